@@ -19,7 +19,9 @@ own slice of the stream, ops are routed to the row's owner shard with all_to_all
 incr kernels of step s and the exchange of incr(s+1) overlaps get(s) (split-phase API on a
 separate communication stream).  scaling = weak.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line (`value`,
+`ms_per_step`); `--full` adds the rest (kernel timers and roofline, cold start, table figures, the all-hits replay, the
+extra legs, random-access ceilings, cpu_baseline).  `--dump-outputs DIR` writes what the last timed step returned.
 """
 import argparse
 import json
@@ -42,6 +44,7 @@ HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s
 
 
 LINE_MAX = 4096           # the ONE stdout line stays below this (the driver scans a bounded window: r03's 20 KB line went unparsed)
+DUMP_SAMPLE = 1 << 21     # --dump-outputs: positions of the last batch written per output (2 x 16 MB of float64)
 
 
 def _r(v, sig=5):
@@ -150,6 +153,29 @@ def emit(full, json_out, name="bench_detail.json"):
             pass
     print("bench detail: " + json.dumps(full, default=str), file=sys.stderr, flush=True)
     print(short_line(full, rel), file=json_out, flush=True)
+
+
+def dump_outputs(torch, d, x, y, out_i, out_g):
+    """--dump-outputs: what the last timed step returned (incr batch, then get batch on the same keys), at a fixed seeded
+    sample of positions, as float64 (exact for uint32).  The get values are final values and do not depend on the order
+    the ops were applied in.  For a key that occurs k times in one incr batch, the batch contract (include/smatrix_batch.h)
+    fixes its k returns as a set but not which position gets which, so incr_returns holds them in canonical form: the
+    returns of each key in ascending order over its positions in index order."""
+    import numpy as np
+    u = lambda t: t.to(torch.int64) & 0xFFFFFFFF
+    key = (u(x) << 32) | u(y)
+    ret = u(out_i)
+    by_pos = torch.sort(key, stable=True).indices                  # grouped by key, index order inside a key
+    q = torch.sort(ret, stable=True).indices
+    by_ret = q[torch.sort(key[q], stable=True).indices]             # grouped by key, ascending return inside a key
+    canon = torch.empty_like(ret)
+    canon[by_pos] = ret[by_ret]
+    n = key.numel()
+    idx = np.sort(np.random.default_rng(SEED).choice(n, min(n, DUMP_SAMPLE), replace=False))
+    at = torch.from_numpy(idx).to(key.device)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "incr_returns.npy"), canon[at].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "get_values.npy"), u(out_g)[at].cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(sample_ops, torch, dev):
@@ -1037,7 +1063,16 @@ def main():
     ap.add_argument("--no-reserve", action="store_true", help="do not map the row arena up front (A/B of smatrix_reserve)")
     ap.add_argument("--sustain-s", type=float, default=1.5, help="seconds of the sustained (continuing-stream) leg")
     ap.add_argument("--batch-leg", type=int, default=0, help="extra leg: the same stream in batches of 2^N ops (e.g. 26), not part of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="config 2 / 4: everything beyond the headline figure -- kernel timers and roofline, cold start, table figures, "
+                         "the all-hits replay, the extra legs, random-access ceilings, cpu_baseline (a plain run only sets up, warms "
+                         "up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 2 / 4: after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; "
+                         "a fixed seeded sample of %d positions of the batch, rank 0's batch at N > 1)" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs applies to config 2 / 4 only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as given: this process becomes a launcher.  It spawns N CHILD interpreters, one
@@ -1279,7 +1314,7 @@ def main():
 
     first_step_ms = None
     for s in range(args.warmup):
-        if s == 0 and not sharded:
+        if s == 0 and not sharded and args.full:
             # the cold start: step 0 creates the rows and doubles the hot ones up to 2^19 cells (untimed warmup; reported as an extra)
             torch.cuda.synchronize(); tc = time.perf_counter()
             step(s)
@@ -1287,15 +1322,19 @@ def main():
         else:
             step(s)
     local_m = m.local if sharded else m
-    local_m.profile(not args.no_profile)          # HIP events around the op kernels, on the stream they run on
+    if args.full:
+        local_m.profile(not args.no_profile)      # HIP events around the op kernels, on the stream they run on
     fence()
     t0 = time.perf_counter()
     for s in range(args.warmup, total_steps):
         step(s)
     fence()
     dt = time.perf_counter() - t0
-    st = local_m.stats()
-    local_m.profile(False)
+    if args.full:
+        st = local_m.stats()
+        local_m.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, xs[total_steps - 1], ys[total_steps - 1], out_i, out_g)
     shard_info = None
     if sharded:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -1317,7 +1356,7 @@ def main():
 
     # informative extra (not `value`): the same step on the finished table -- every incr is a hit
     steady = None
-    if not sharded:
+    if not sharded and args.full:
         fence()
         t1 = time.perf_counter()
         for s in range(total_steps - 4, total_steps):
@@ -1328,12 +1367,12 @@ def main():
                   "note": "last 4 batches replayed on the 100.4M-nnz table: no inserts, no growth"}
 
     # parity spot-check inside the bench: the last get batch must equal the last incr returns' per-key max
-    ok = bool((out_g >= 1).all().item())
+    ok = bool((out_g >= 1).all().item()) if args.full else None
 
     extras = {}
     if not sharded and args.batch_leg:
         extras["batch_2_%d" % args.batch_leg] = guarded(batch_size_leg, torch, dev, args.batch_leg, stream)
-    if not sharded and not args.no_extras and args.batch_lg == BATCH_LG:
+    if not sharded and args.full and not args.no_extras and args.batch_lg == BATCH_LG:
         # (1) the reference-held checksums of this very stream, on a fresh matrix (outside the timed region)
         # (2) sustained leg: the SAME step on the continuing stream (fresh batches, table keeps growing) for >= 1 s of
         #     back-to-back steps, so that the run holds a timed region far longer than any sampling period -- once right
@@ -1372,8 +1411,9 @@ def main():
                                       "and step, exchange over RCCL/xGMI" % (world, args.batch_lg)),
                    "ids_per_axis": n_ids,
                    "batch_ops": B, "arena_reserved_bytes": ARENA_RESERVE, "distinct_batches": ring, "parallelism": "row-hash shards x%d" % world if sharded else "single GPU"},
-        "sanity_all_gets_positive": ok,
     }
+    if args.full:
+        res["sanity_all_gets_positive"] = ok
     if sharded:
         res["config"]["router"] = ("c-library/%s" % m.transport) if args.c_router else "torch.distributed/%s" % args.backend
         res["config"]["rccl"] = rccl_library_in_use()            # which RCCL served the exchange: path and ncclGetVersion()
@@ -1382,7 +1422,7 @@ def main():
     if shard_info:
         res["config"]["placement"] = shard_info
     res.update(extras)
-    if rank == 0:
+    if rank == 0 and args.full:
         ki = st["kernel_ms_incr"] / max(st["kernel_launches_incr"], 1)
         kg = st["kernel_ms_get"] / max(st["kernel_launches_get"], 1)
         # per-launch units: rank 0's local launches (N=1: exactly B ops per launch)
@@ -1446,6 +1486,7 @@ def main():
             res["random_access"] = ra
         if world == 1 and not args.no_cpu:
             res["cpu_baseline"] = cpu_baseline(1 << args.cpu_sample_lg, torch, dev)
+    if rank == 0:
         emit(res, json_out)
     if comm is not None:
         comm.shutdown()

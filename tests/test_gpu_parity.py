@@ -560,7 +560,7 @@ def test_sharded_path_one_rank_nccl():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-sharded", "--batch-lg", "18",
-                        "--steps", "3", "--warmup", "1", "--no-cpu"], capture_output=True, text=True, timeout=600)
+                        "--steps", "3", "--warmup", "1", "--no-cpu", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
@@ -976,7 +976,7 @@ def test_bench_launch_contract_n_ranks(world, router):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--batch-lg", "18" if world == 2 else "20", "--backend", "gloo", "--single-device"] + (["--py-router"] if router == "python" else [])
+           "--batch-lg", "18" if world == 2 else "20", "--backend", "gloo", "--single-device", "--full"] + (["--py-router"] if router == "python" else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]

@@ -37,8 +37,8 @@ bytes_agg = (agg["fetch"] + agg["write"]) * 1024; bytes_get = (get["fetch"] + ge
 rd_agg = agg["miss"] - agg["atom"]
 t_agg = rd_agg / (R * 1e9) + agg["atom"] / (A * 1e9); t_get = get["miss"] / (R * 1e9)
 ki, kg = b["roofline"]["avg_launch_ms"], b["roofline_get"]["avg_launch_ms"]
-hdr = """# rocprofv3 --kernel-trace --pmc <counter> --output-format csv -- python3 bench.py --no-cpu --no-extras   (three separate passes: FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum TCC_EA0_ATOMIC_sum; tools/refresh_profiles.sh + tools/build_profiles.py)
-# MI355X, round 6, bench.py --no-cpu --no-extras: config 2 = 24 batches of 2^24 ops (+ 4 replayed batches of the steady-state extra).  FETCH_SIZE/WRITE_SIZE are KiB per dispatch, means over the dispatches listed.
+hdr = """# rocprofv3 --kernel-trace --pmc <counter> --output-format csv -- python3 bench.py --full --no-cpu --no-extras   (three separate passes: FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum TCC_MISS_sum TCC_EA0_ATOMIC_sum; tools/refresh_profiles.sh + tools/build_profiles.py)
+# MI355X, round 6, bench.py --full --no-cpu --no-extras: config 2 = 24 batches of 2^24 ops (+ 4 replayed batches of the steady-state extra).  FETCH_SIZE/WRITE_SIZE are KiB per dispatch, means over the dispatches listed.
 # Calibration in our own access pattern, same runs: k_probe_random<0> = 2^27 random 8-byte loads over 4 GiB -> %.0f KiB = %.1f B per touch
 #   (a 64 B line per touch; no 1/2 correction for this shape); k_probe_random<1>/<2> = 2^27 scattered 32-bit atomics -> WRITE_SIZE 32 B and TCC_EA0_ATOMIC 1.0 per atomic.
 #   (the guide's gfx950 correction -- FETCH_SIZE tallies a 128-B coalesced streaming request at 64 B -- applies only to the streamed op arrays,
@@ -63,14 +63,14 @@ hdr = """# rocprofv3 --kernel-trace --pmc <counter> --output-format csv -- pytho
        100 * t_agg * 1e3 / ki, get["miss"] / 1e6, R, t_get * 1e3, kg, 100 * t_get * 1e3 / kg)
 open(os.path.join(P, RND + "_pmc_summary.txt"), "w").write(hdr + raw)
 json.dump({"summary": "profiles/%s_pmc_summary.txt" % RND, "kernel_source_sha16": kernel_source_sha16(),
-           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / TCC_* in separate passes of `python3 bench.py --no-cpu --no-extras`",
+           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / TCC_* in separate passes of `python3 bench.py --full --no-cpu --no-extras`",
            "k_apply_agg_incr": {"fetch_kib": agg["fetch"], "write_kib": agg["write"], "bytes_per_launch": int(bytes_agg), "ops_per_launch": N,
                                 "l2_misses": agg["miss"], "memory_side_atomics": agg["atom"]},
            "k_apply_get": {"fetch_kib": get["fetch"], "write_kib": get["write"], "bytes_per_launch": int(bytes_get), "ops_per_launch": N,
                            "l2_misses": get["miss"]}}, open(os.path.join(P, "pmc.json"), "w"), indent=1)
 ur = json.load(open(os.path.join(G, "prof_bench_under_rocprof.json")))
 open(os.path.join(P, RND + "_rocprof_kernel_stats.txt"), "w").write(
-    "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu --no-extras   (MI355X, round 6, tools/refresh_profiles.sh; bench line of this "
+    "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu --no-extras   (MI355X, round 6, tools/refresh_profiles.sh; bench line of this "
     "same profiled run: %.0f Mops/s, k_apply_agg<INCR> round-0 avg %.3f ms and k_apply<GET> %.3f ms by HIP events; the full-batch grids below include the 4 all-hit "
     "replays of the steady-state extra and the first batches of the empty table)\n" % (ur["value"], ur["roofline"]["avg_launch_ms"], ur["roofline_get"]["avg_launch_ms"])
     + open(os.path.join(G, "prof_kernel_stats.txt")).read()

@@ -6,10 +6,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 # (bench.py prints the SHORT line; the full result -- what tools/build_profiles.py reads -- is bench_detail.json)
-python3 $R/bench.py > $O/prof_bench_line.json 2> $O/prof_bench.err
+python3 $R/bench.py --full > $O/prof_bench_line.json 2> $O/prof_bench.err
 cp $R/bench_detail.json $O/prof_bench.json
 # config 2: kernel stats + spans + timeline
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --no-cpu --no-extras > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --full --no-cpu --no-extras > /dev/null 2>&1
 cp $R/bench_detail.json $O/prof_bench_under_rocprof.json
 python3 $R/tools/prof_summary.py $O/kt $O/prof_kernel_stats.txt
 python3 $R/tools/step_spans.py $O/kt > $O/prof_step_spans.txt
@@ -23,7 +23,7 @@ rm -rf $O/kt3
 # PMC passes (one counter set per run)
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum TCC_EA0_ATOMIC_sum"; do
   tag=$(echo $c | cut -d' ' -f1)
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --no-cpu --no-extras > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --full --no-cpu --no-extras > /dev/null 2>&1
 done
 python3 $R/tools/pmc_summary.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_TCC_HIT_sum > $O/prof_pmc_raw.txt
 rm -rf $O/pmc_*
