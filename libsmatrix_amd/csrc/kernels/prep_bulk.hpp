@@ -39,7 +39,9 @@ __device__ __forceinline__ void prep_body(
     const uint32_t* __restrict__ ys, GrowTask* tasks, uint32_t* klist, uint32_t kcap, uint32_t* rebal,
     FreeLists fl, uint32_t st, uint32_t create_only, uint32_t wpo_max, uint2* pend_rec = nullptr, uint32_t pend_rec_cap = 0, uint32_t* pend_ctl = nullptr) {
   // pend_rec (round 6, clustered matrices): every op whose key is ABSENT leaves {directory slot, key} there (pend_ctl[0] counts
-  //             them): the rows that double in this round take these keys in as they are rebuilt (k_pend_group, growth.hpp)
+  //             them): the rows that double in the growth round right behind THIS prep take these keys in as they are rebuilt
+  //             (k_pend_group, growth.hpp); no later growth round reads them (a cold start may have inserted the keys since,
+  //             grow_directory may have moved the slots)
   // wpo_max (clustered matrices): a list of at most so many ops is taken a WAVE per op -- lane 0 holds the op, the wave finishes
   //             its long probe -- like k_apply_wpo: a few hundred deferred ops of big clustered rows, 64 to a wave, walked their
   //             10^4..10^5 cells one lane after the other (7-16 ms for 300-700 ops of the dense-id stream's late rounds)

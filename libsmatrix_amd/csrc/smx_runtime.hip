@@ -718,8 +718,7 @@ struct Matrix {
   DevBuf<unsigned long long> pend_hash;
   double w_call_s = 0, w_wait_s = 0, w_alloc_s = 0;      // write batches: wall time inside run_write, of it waiting for the device, of it in device allocations / frees
   bool pend_on = true;                  // SMATRIX_PEND=0: the keys that wait for a doubling go in through the retry, as in round 5
-  bool pend_armed = false;              // the prep that has just been enqueued left records (the growth round that follows groups them)
-  uint32_t pend_est = 0;                // ... about so many
+  uint32_t pend_est = 0;                // records the last prep that left any may have written, about so many
   DevBuf<uint32_t> big_list;            // [0] = n, then the directory slots of the rows of >= 2^FAR_ROW_LG cells (k_far_rows rebuilds it, k_grow_commit appends)
   bool big_list_valid = false;          // ... complete for the directory as it stands (not after a rebuild of the directory or a file load)
   DevBuf<uint2> far_unit_info;          // per unit: its row's block, size and its place in the row (k_far_rows -> k_far_scan)
@@ -841,6 +840,8 @@ void grow_directory(Matrix* m, uint32_t factor, hipStream_t s) {
   HIP_OK(hipStreamSynchronize(s));
   HIP_OK(dev_free(m->d_dir));
   m->d_dir = nd;
+  if (m->trace_rounds)
+    fprintf(stderr, "[smatrix] batch %llu directory grown: %u -> %u slots (rows=%u)\n", (unsigned long long)m->st.batches, m->dir_size, ns, m->dir_used);
   m->dir_size = ns;
   m->st.dir_grown++;
 }
@@ -1111,7 +1112,10 @@ hipEvent_t get_timing_event(Matrix* m) {
 // nt / gu / nk: what prep has counted (read back), or -- `spec` -- the host's ESTIMATES for a round whose counters it has
 // not read: every buffer is sized for them, the launches get grids for them (the kernels loop over the device-side
 // counts), and k_grow_plan refuses what does not fit.
-void grow_rows(Matrix* m, hipStream_t s, uint32_t nt, uint64_t gu, const uint32_t* nk, bool spec) {
+// pend: the prep right in front of this growth round left waiting-key records (run_write's launch_prep).  Records of any
+// older prep are stale -- their keys may have been inserted since (a cold start), their directory slots may name other
+// rows (grow_directory) -- and the kernels that take them in do not look for duplicates.
+void grow_rows(Matrix* m, hipStream_t s, uint32_t nt, uint64_t gu, const uint32_t* nk, bool spec, bool pend_prep) {
   ensure_arena_free(m, gu, s);
   // chunk bounds: a table of 2^lg cells has max(1, 2^lg/64) chunks; units = 2^lg/16
   m->map_new.need((size_t)nt + gu / 4 + 1);
@@ -1128,8 +1132,7 @@ void grow_rows(Matrix* m, hipStream_t s, uint32_t nt, uint64_t gu, const uint32_
   // (spec: the arena holds gu units beyond the host's mirror of the bump pointer -- row creation in prep may have taken
   //  some of the slack ensure_arena_free was asked for, hence the cap is what is mapped, checked per allocation)
   // the keys that wait for these doublings (k_prep's records): buckets by the plan, grouped right behind it
-  const bool pend = m->pend_armed && m->clustered && m->home_on;
-  m->pend_armed = false;
+  const bool pend = pend_prep && m->clustered && m->home_on;
   uint32_t pend_hash_lg = 16;
   if (pend) {
     m->pend_keys.need(std::min<uint64_t>(8ull * nt + 4ull * gu + 1024, 0x7FFFFFFFull));
@@ -1562,7 +1565,7 @@ bool insert_pending_keys(Matrix* m, const uint32_t* list, uint32_t n_list, const
     stalled = progress ? 0 : stalled + 1;
     rows_before = m->dir_used;
     m->st.deferred_ops += nd;
-    if (c.n_tasks) grow_rows(m, s, c.n_tasks, c.grow_units, c.n_kind, false);
+    if (c.n_tasks) grow_rows(m, s, c.n_tasks, c.grow_units, c.n_kind, false, false);     // (k_prep above left no records)
     if (c.n_rebal) {
       hipLaunchKernelGGL(k_rebal, dim3(std::min<uint32_t>(blocks_for(c.n_rebal, 64), 1024)), dim3(64), 0, s, m->d_ctl, m->rebal.p, m->d_dir, m->arena.base);
       HIP_OK(hipGetLastError());
@@ -1703,6 +1706,7 @@ void run_write(Matrix* m, int op, uint32_t n, const uint32_t* x, const uint32_t*
         continue;
       }
     }
+    bool prep_pend = false;               // the prep enqueued last in this round left waiting-key records (for the growth round behind it)
     const auto launch_prep = [&](const uint32_t* list) {
       // (a short list of a clustered matrix is taken a wave per op: the grid covers 64 lanes per op then)
       const uint32_t pgrid = m->clustered && cur_n <= 8192u ? blocks_for((uint64_t)cur_n * 64, PREP_THREADS) : blocks_for(cur_n, PREP_THREADS);
@@ -1714,7 +1718,7 @@ void run_write(Matrix* m, int op, uint32_t n, const uint32_t* x, const uint32_t*
         HIP_OK(hipMemsetAsync(m->pend_ctl.p, 0, 16, s));
         m->pend_est = (uint32_t)std::min<uint64_t>(chained ? std::max<uint64_t>(2ull * m->spec_nd_prev, 1u << 16) : cur_n, m->pend_rec.cap);
       }
-      m->pend_armed = pend;
+      prep_pend = pend;
       hipLaunchKernelGGL(k_prep, dim3(std::min<uint32_t>(pgrid, m->prep_blocks)), dim3(PREP_THREADS), 0, s,
                          m->d_ctl, m->d_dir, m->dir_size - 1, dir_limit, m->arena.base,
                          (uint64_t)(m->arena.mapped / UNIT_BYTES), list, x, y, m->tasks.p, m->klist.p, m->klist_cap,
@@ -1769,7 +1773,7 @@ void run_write(Matrix* m, int op, uint32_t n, const uint32_t* x, const uint32_t*
       const uint32_t est_nk[4] = {std::max<uint32_t>(2 * m->spec_nk_prev[0], 4096), std::max<uint32_t>(2 * m->spec_nk_prev[1], 1024),
                                   std::max<uint32_t>(2 * m->spec_nk_prev[2], 256), std::max<uint32_t>(2 * m->spec_nk_prev[3], 64)};
       const uint64_t host_next = m->arena_next;
-      grow_rows(m, s, est_nt, est_gu, est_nk, true);
+      grow_rows(m, s, est_nt, est_gu, est_nk, true, prep_pend);
       m->arena_next = host_next;                              // (the mirror is refreshed by the read-back below)
       hipLaunchKernelGGL(k_round_advance, dim3(1), dim3(64), 0, s, m->d_ctl, m->rebal.p, m->d_dir, m->arena.base);
       // the retry: lane per op over the device-side list (its length is ctl->n_prev), grid for 4x the previous batch's
@@ -1905,7 +1909,7 @@ void run_write(Matrix* m, int op, uint32_t n, const uint32_t* x, const uint32_t*
       m->spec_nt_prev = m->h_ctl->n_tasks; m->spec_gu_prev = m->h_ctl->grow_units;
       for (int k = 0; k < 4; k++) m->spec_nk_prev[k] = m->h_ctl->n_kind[k];
     }
-    if (m->h_ctl->n_tasks) grow_rows(m, s, m->h_ctl->n_tasks, m->h_ctl->grow_units, m->h_ctl->n_kind, false);
+    if (m->h_ctl->n_tasks) grow_rows(m, s, m->h_ctl->n_tasks, m->h_ctl->grow_units, m->h_ctl->n_kind, false, prep_pend);   // (records of this round's last prep: the chain's retry's)
     if (m->h_ctl->n_rebal) {
       hipLaunchKernelGGL(k_rebal, dim3(std::min<uint32_t>(blocks_for(m->h_ctl->n_rebal, 64), 1024)), dim3(64), 0, s,
                          m->d_ctl, m->rebal.p, m->d_dir, m->arena.base);
