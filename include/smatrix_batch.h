@@ -110,6 +110,29 @@ int smatrix_cf_import_sessions(smatrix_t* self, size_t n_sessions, const uint64_
 int smatrix_cf_import_sessions_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
                                    const uint64_t* d_op_offsets, uint64_t total_ops, void* hip_stream);
 
+/* ---- whole-matrix export ------------------------------------------------- */
+enum { SMATRIX_EXPORT_TABLE = 0, SMATRIX_EXPORT_SORTED = 1 };
+
+/* Every row of the matrix and every pair its getrow would return, as CSR:
+ *   rows[i]                      row id, i < n_rows
+ *   row_ptr[i] .. row_ptr[i+1]   its pairs, at pairs + 2*row_ptr[i] (uint32 units; {column, value}, the getrow_batch layout)
+ * TABLE:  rows in directory-slot order; each row's pairs in table-slot order, byte-identical to smatrix_getrow_batch of that
+ *         row with an unlimited buffer.  Deterministic for a given table state.
+ * SORTED: rows ascending by id, pairs ascending by column.  Depends only on the matrix's contents, not on its history.
+ * Row set = the ids x for which smatrix_row_info(x) returns 1: a row with no pairs (quirk Q3, set(x,0,0) on a new row) is
+ * listed with row_ptr[i] == row_ptr[i+1].  A row's pair count is its number of non-empty slots, NOT rowlen (quirks Q1/Q5).
+ * row_ptr == NULL: size query -- writes *n_rows, *nnz, returns 0.
+ * Returns 0 when written; 1 when n_rows > cap_rows or nnz > cap_nnz (nothing written, *n_rows / *nnz = what is needed);
+ * -1 for an unknown order.  row_ptr must hold cap_rows + 1 entries.  n_rows / nnz are HOST pointers in both flavours.
+ * Both take the matrix lock for their whole run; scalar writes still held in the host mirror are written back first.
+ * _dev: buffers in device memory on the matrix's GPU, work on hip_stream (NULL = the legacy default stream); the call returns
+ * after the export has completed on that stream (it reads the sizes back). */
+int smatrix_export(smatrix_t* self, int order, uint64_t cap_rows, uint64_t cap_nnz,
+                   uint32_t* rows, uint64_t* row_ptr, uint32_t* pairs, uint64_t* n_rows, uint64_t* nnz);
+int smatrix_export_dev(smatrix_t* self, int order, uint64_t cap_rows, uint64_t cap_nnz,
+                       uint32_t* d_rows, uint64_t* d_row_ptr, uint32_t* d_pairs,
+                       uint64_t* n_rows, uint64_t* nnz, void* hip_stream);
+
 /* Capacity hint, like vector::reserve: map at least `bytes` of device memory for row tables now instead of in growth
  * steps later (each step is a call into the driver, normally ~0.3 ms, but one that can block for seconds while the driver
  * still has freed memory to wipe).  Nothing observable changes.  Returns 0. */

@@ -73,6 +73,8 @@ def load():
         "smatrix_cf_topk_batch_dev": (C.c_int, [H, C.c_size_t, V, C.c_uint32, V, V, V, V]),
         "smatrix_cf_import_sessions": (C.c_int, [H, C.c_size_t, u64p, u32p]),
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
+        "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),
+        "smatrix_export_dev": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, V, V, V, u64p, u64p, V]),
         "smatrix_stats": (None, [H, C.POINTER(Stats)]),
         "smatrix_stats_sz": (None, [H, C.POINTER(Stats), C.c_size_t]),
         "smatrix_profile": (None, [H, C.c_int]),

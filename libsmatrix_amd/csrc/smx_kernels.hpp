@@ -31,6 +31,7 @@ namespace smx {
 #include "kernels/prep_bulk.hpp"
 #include "kernels/growth.hpp"
 #include "kernels/rows.hpp"
+#include "kernels/export.hpp"
 #include "kernels/io_router.hpp"
 #include "kernels/probes.hpp"
 

@@ -7,12 +7,22 @@ batched calls (include/smatrix_batch.h) that feed the HIP kernels.  Everything
 runs on the GPU through lib/smatrix.so; there is no CPU path here.
 """
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 
 from . import _lib
 
 OP_GET, OP_SET, OP_INCR, OP_DECR = 0, 1, 2, 3
+EXPORT_TABLE, EXPORT_SORTED = 0, 1      # include/smatrix_batch.h SMATRIX_EXPORT_*
+_EXPORT_ORDERS = {"table": EXPORT_TABLE, "sorted": EXPORT_SORTED}
+
+
+def _export_order(order):
+    if order not in _EXPORT_ORDERS:
+        raise ValueError("order must be 'sorted' or 'table', not %r" % (order,))
+    return _EXPORT_ORDERS[order]
 
 
 def _u32(a):
@@ -28,6 +38,10 @@ class SparseMatrix:
         """filename None = in-memory (SparseMatrix.java:70-77); else open-or-create the file."""
         self._lib = _lib.load()
         self.filename = filename
+        env = os.environ.get("SMATRIX_DEVICE")
+        self._device = int(env) if env else None      # the matrix's GPU: SMATRIX_DEVICE, else the current device at open
+        if self._device is None and "torch" in sys.modules and sys.modules["torch"].cuda.is_initialized():
+            self._device = sys.modules["torch"].cuda.current_device()
         self._h = self._lib.smatrix_open(filename.encode() if filename else None)
         if not self._h:
             # smatrix_jni.c:61-62 turns a NULL handle into IllegalArgumentException
@@ -193,6 +207,63 @@ class SparseMatrix:
 
     def cf_neighbors_batch_dev(self, n, items_ptr, off_ptr, ids_ptr, scores_ptr, cnt_ptr, stream=None):
         self._lib.smatrix_cf_neighbors_batch_dev(self._h, n, items_ptr, off_ptr, ids_ptr, scores_ptr, cnt_ptr, stream)
+
+    # ---- whole-matrix export (include/smatrix_batch.h smatrix_export) -------------------
+    def export(self, order="sorted"):
+        """every row and its pairs as CSR: -> (rows uint32[n], row_ptr uint64[n+1], pairs uint32[nnz, 2] {column, value}).
+        "sorted": rows by id, pairs by column; "table": directory-slot order, each row's pairs in table-slot order
+        (getrow_batch's bytes).  A size query, then the export; a matrix that grew in between raises."""
+        o = _export_order(order)
+        n, nnz = C.c_uint64(0), C.c_uint64(0)
+        self._lib.smatrix_export(self._h, o, 0, 0, None, None, None, C.byref(n), C.byref(nnz))
+        rows = np.zeros(n.value, np.uint32)
+        row_ptr = np.zeros(n.value + 1, np.uint64)
+        pairs = np.zeros((nnz.value, 2), np.uint32)
+        n2, nnz2 = C.c_uint64(0), C.c_uint64(0)
+        rc = self._lib.smatrix_export(self._h, o, n.value, nnz.value, _p(rows), row_ptr.ctypes.data_as(_lib.u64p),
+                                      pairs.ctypes.data_as(_lib.u32p), C.byref(n2), C.byref(nnz2))
+        if rc != 0:
+            raise RuntimeError("smatrix_export: the matrix grew between the size query (%d rows, %d pairs) and the export "
+                               "(%d rows, %d pairs)" % (n.value, nnz.value, n2.value, nnz2.value))
+        return rows, row_ptr, pairs
+
+    def export_dev(self, order="sorted", stream=None):
+        """the same on the matrix's GPU: -> torch tensors (rows int32[n] (the uint32 ids' bits), row_ptr int64[n+1],
+        pairs int32[nnz, 2]).  stream: a torch.cuda.Stream (None: the legacy default stream); the export has completed on it
+        when this returns."""
+        import torch
+        o = _export_order(order)
+        dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+        sp = stream.cuda_stream if stream is not None else None
+        n, nnz = C.c_uint64(0), C.c_uint64(0)
+        self._lib.smatrix_export_dev(self._h, o, 0, 0, None, None, None, C.byref(n), C.byref(nnz), sp)
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.default_stream(dev)):
+            rows = torch.empty(n.value, dtype=torch.int32, device=dev)
+            row_ptr = torch.empty(n.value + 1, dtype=torch.int64, device=dev)
+            pairs = torch.empty((nnz.value, 2), dtype=torch.int32, device=dev)
+        n2, nnz2 = C.c_uint64(0), C.c_uint64(0)
+        rc = self._lib.smatrix_export_dev(self._h, o, n.value, nnz.value, rows.data_ptr(), row_ptr.data_ptr(), pairs.data_ptr(),
+                                          C.byref(n2), C.byref(nnz2), sp)
+        if rc != 0:
+            raise RuntimeError("smatrix_export_dev: the matrix grew between the size query (%d rows, %d pairs) and the export "
+                               "(%d rows, %d pairs)" % (n.value, nnz.value, n2.value, nnz2.value))
+        return rows, row_ptr, pairs
+
+    def to_sparse_coo(self, size=None):
+        """the matrix as a coalesced torch.sparse_coo_tensor on its GPU, from the SORTED export: indices int64 [2, nnz]
+        (row, column), values int64 (the uint32 values, zero-extended).  size: default (largest row id + 1, largest column
+        + 1) -- torch needs rows * columns < 2**63, so the whole id space (2**32, 2**32) is not a shape it can hold."""
+        import torch
+        rows, row_ptr, pairs = self.export_dev("sorted")
+        mask = 0xFFFFFFFF
+        x = torch.repeat_interleave(rows.to(torch.int64) & mask, row_ptr[1:] - row_ptr[:-1])
+        y = pairs[:, 0].to(torch.int64) & mask
+        v = pairs[:, 1].to(torch.int64) & mask
+        if size is None:
+            size = (int(x.max().item()) + 1 if x.numel() else 0, int(y.max().item()) + 1 if y.numel() else 0)
+        if size[0] * size[1] >= 1 << 63:
+            raise ValueError("to_sparse_coo: a %d x %d tensor is beyond torch's element count (rows * columns < 2**63)" % tuple(size))
+        return torch.sparse_coo_tensor(torch.stack([x, y]), v, size=tuple(size), is_coalesced=True)
 
     # ---- introspection --------------------------------------------------------
     def stats(self):
