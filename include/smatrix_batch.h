@@ -100,6 +100,29 @@ int smatrix_cf_topk_batch(smatrix_t* self, size_t n, const uint32_t* items, uint
 int smatrix_cf_topk_batch_dev(smatrix_t* self, size_t n, const uint32_t* d_items, uint32_t k, uint32_t* d_ids,
                               double* d_scores, uint32_t* d_counts, void* hip_stream);
 
+/* Session recommendations ("people who viewed these also viewed"): the k <= 64 best items for each session (a user's or
+ * a basket's items), the whole query fused on the GPU.  Session s is items[offsets[s] .. offsets[s+1]) (n_sessions + 1
+ * offsets; a session holds fewer than 2^32 items).
+ *   items      duplicates count once, at their first position; an item with no row contributes nothing.
+ *   candidates every b that is the key of a non-empty cell in the row of some session item a, with b != 0 (column 0
+ *              holds the totals) and b not itself an item of the session (a row can hold its own id: the import counts
+ *              an id that occurs twice in a session against itself).
+ *   score(b)   the sum over the session's distinct items a whose row holds b of cf_cosine(a, b), each term exactly as
+ *              smatrix_cf_neighbors_batch computes it (get(b,0) == 0 -> 1; den == 0 -> 0; cc > den -> 0), added in
+ *              session order (first positions) from 0.0, in double: bit-equal to a left-to-right sum of those doubles.
+ *   output     the k best candidates, score descending, equal scores by ascending id: the result depends only on the
+ *              matrix's contents.  ids / scores hold n_sessions*k entries, session s's at [s*k, s*k + counts[s]);
+ *              counts[s] = min(k, candidates).  The host flavour zero-fills the unused entries; _dev leaves them.
+ * Returns -1 for k == 0, k > 64 or n_sessions >= 2^32, 0 otherwise.  Takes the matrix lock and sees values the scalar
+ * calls still hold in the host mirror; file-backed matrices work unchanged.  The same contents and input give the same
+ * bytes on every call.
+ * _dev: all arrays in device memory, on hip_stream (NULL: the legacy default stream, synchronised before returning).  The
+ * matrix's scratch is shared by all calls: a call's work waits on the stream for the previous call's, whatever its stream. */
+int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                               uint32_t k, uint32_t* ids, double* scores, uint32_t* counts);
+int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                   uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

@@ -1,0 +1,429 @@
+// kernels/recommend.hpp -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch): per session, the k best
+// items over the union of its items' rows, a candidate b scored by the sum, in session order, of cf_cosine(a, b) over the session's
+// distinct items a whose row holds b.  Host side: smx_recommend.inc.
+// A fragment of smx_kernels.hpp: included there, after rows.hpp (CfCand, cf_sort64, cf_merge_stages), INSIDE namespace smx.
+//
+// Every session is summed in a hash of its own.  A slot holds {key, sqrt(get(b,0)) or -1 for an item of the session, running sum}:
+// the session's items go in first (excluded keys; an item's FIRST position is kept in the low word of its sum as 2^32-1 - pos, by
+// atomicMax), then the items' rows are scanned one item at a time in session order, with a barrier (LDS tier) or a kernel boundary
+// (global tier) between items.  A key appears once in a row, so a slot receives at most one term per item: the sum is a
+// left-to-right sum in session order, whatever the order of lanes.  The terms are added with atomics only so that a row holding
+// a key twice (the reference's reload can leave one) still adds both terms.
+//   k_rec_bound     a wave per session: bound = sum of its distinct items' row sizes (slots: every quirk row is covered); tiers
+//   k_rec_lds       a workgroup per session of bound + length <= REC_LDS_SLOTS: the hash in LDS, the top-k at the end
+//   k_rec_gl_*      the other sessions: hashes in a pooled device buffer, a launch per item position, a wave per 512-cell chunk
+//                   of a row; then a wave per 4096-slot segment (its top-64) and a workgroup per session (the merge)
+
+constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
+constexpr uint32_t REC_LDS_THREADS = 512;
+constexpr uint32_t REC_SEG = 4096;            // global tier: slots per top-k segment; global tables are multiples of it
+constexpr uint32_t REC_GL_MIN_LG = 13;        // ... and at least 8192 slots (the bound of such a session is above 4096)
+constexpr uint32_t REC_CHUNK = 512;           // global tier: cells of a row per wave task
+constexpr uint32_t REC_MERGE_THREADS = 1024;
+
+struct RecCtl {
+  uint32_t n_lds, n_big, max_len, pad;
+  unsigned long long total_slots, max_slots;  // global tier: table slots of all its sessions, of the largest one
+};
+
+// (score desc, id asc): the result order of smatrix_cf_recommend_batch
+struct CfById {
+  __device__ __forceinline__ bool operator()(const CfCand& a, const CfCand& b) const {
+    return a.key > b.key || (a.key == b.key && a.id < b.id);
+  }
+};
+
+// one term, exactly as k_cf_neighbors computes it (sqb = sqrt of get(b,0), 0 counted as 1)
+__device__ __forceinline__ double rec_term(uint32_t cc, double sa, double sqb) {
+  const double num = (double)cc;
+  const double den = sa * sqb;
+  return (den != 0.0 && !(num > den)) ? num / den : 0.0;
+}
+__device__ __forceinline__ double rec_sqrt_total(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t b) {
+  bool dummy = false;
+  uint32_t t = apply_one<OP_GET>(dir, dmask, arena, b, 0u, 0u, &dummy);
+  if (t == 0) t = 1;
+  return sqrt((double)t);
+}
+__device__ __forceinline__ uint32_t rec_lg(uint64_t need, uint32_t min_lg) {
+  uint32_t lg = min_lg;
+  while ((1ull << lg) < need) lg++;
+  return lg;
+}
+__device__ __forceinline__ uint32_t rec_first_word(uint64_t pos) { return 0xffffffffu - (uint32_t)pos; }
+
+// find or claim key b (!= 0) in a hash of mask + 1 slots (never full: it has room for every key it can be given)
+template <bool LDS>
+__device__ __forceinline__ uint32_t rec_slot(uint32_t* keys, uint32_t mask, uint32_t b, bool* claimed) {
+  uint32_t h = fmix32(b) & mask;
+  for (;;) {
+    const uint32_t c = LDS ? __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+                           : __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c == b) { *claimed = false; return h; }
+    if (c == 0) {
+      const uint32_t old = atomicCAS(&keys[h], 0u, b);
+      if (old == 0) { *claimed = true; return h; }
+      if (old == b) { *claimed = false; return h; }
+    }
+    h = (h + 1) & mask;
+  }
+}
+// the slot of a key that is there (an item of the session)
+__device__ __forceinline__ uint32_t rec_find(const uint32_t* keys, uint32_t mask, uint32_t b) {
+  uint32_t h = fmix32(b) & mask;
+  while (keys[h] != b) h = (h + 1) & mask;
+  return h;
+}
+__device__ __forceinline__ uint32_t rec_low_word(const double* p) { return *reinterpret_cast<const uint32_t*>(p); }
+
+// ---- tiers ----------------------------------------------------------------------------------------------------------------
+// bound = the sum of the row sizes (slots) of the session's DISTINCT items: every candidate is a non-empty cell of one of
+// those rows, whatever quirk the row carries.  Duplicates are found exactly for sessions of up to REC_DEDUP_MAX items
+// (a wave compares every position with all earlier ones); a longer session counts a repeated row again, and its bound is
+// cut to all_cells, the cells the arena can hold (no session has more candidates than the matrix has cells).  A table never
+// needs more than 2^32 slots: its keys are distinct non-zero 32-bit ids.
+// A session with no row at all has no candidate: its count is written here.  tlg[s] = log2 of the session's table size.
+constexpr uint64_t REC_DEDUP_MAX = 8192;
+constexpr uint32_t REC_MAX_LG = 32;
+
+__global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask, uint32_t n, const uint64_t* __restrict__ off,
+                                                   const uint32_t* __restrict__ items, uint64_t all_cells, RecCtl* ctl,
+                                                   uint32_t* lds_list, uint8_t* tlg, uint32_t* big_list, unsigned long long* big_off,
+                                                   uint32_t* __restrict__ counts) {
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t s = wave; s < n; s += nwaves) {
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    const bool exact = L <= REC_DEDUP_MAX;
+    uint64_t bound = 0;
+    for (uint64_t c0 = 0; c0 < L; c0 += 64) {                       // (wave-uniform loops: the shuffles need every lane)
+      const uint64_t i = c0 + lane;
+      const uint32_t a = i < L ? items[b0 + i] : 0u;
+      uint64_t sz = 0;
+      uint4 sn;
+      if (i < L && dir_find(dir, dmask, a, &sn) && sn.z != 0) sz = 1ull << meta_lg(sn.x);
+      if (exact && __any(sz != 0)) {
+        bool dup = false;
+        for (uint64_t e0 = 0; e0 <= c0; e0 += 64) {                 // the positions before mine, 64 at a time
+          const uint32_t e = e0 + lane < L ? items[b0 + e0 + lane] : 0u;
+          const uint32_t lim = e0 == c0 ? lane : 64u;
+          for (uint32_t j = 0; j < 64; j++) {
+            const uint32_t o = (uint32_t)__shfl((int)e, (int)j);
+            dup |= j < lim && o == a;
+          }
+        }
+        if (dup) sz = 0;
+      }
+      bound += sz;
+    }
+    for (uint32_t d = 32; d; d >>= 1) bound += __shfl_xor(bound, d);
+    if (lane != 0) continue;
+    if (bound == 0) { counts[s] = 0; continue; }
+    if (bound > all_cells) bound = all_cells;
+    uint64_t need = bound + L;
+    if (need > (1ull << REC_MAX_LG)) need = 1ull << REC_MAX_LG;
+    if (need <= REC_LDS_SLOTS) {
+      tlg[s] = (uint8_t)rec_lg(need, 6);
+      lds_list[atomicAdd(&ctl->n_lds, 1u)] = s;
+    } else {
+      const uint32_t lg = rec_lg(need, REC_GL_MIN_LG);
+      tlg[s] = (uint8_t)lg;
+      const uint32_t idx = atomicAdd(&ctl->n_big, 1u);
+      big_list[idx] = s;
+      big_off[idx] = atomicAdd(&ctl->total_slots, 1ull << lg);
+      atomicMax(&ctl->max_slots, 1ull << lg);
+      atomicMax(&ctl->max_len, (uint32_t)L);
+    }
+  }
+}
+
+// ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                             const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                             const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                             uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                             uint32_t* __restrict__ counts) {
+  __shared__ uint32_t s_key[REC_LDS_SLOTS];
+  __shared__ double s_sq[REC_LDS_SLOTS];
+  __shared__ double s_sum[REC_LDS_SLOTS];
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  constexpr uint32_t NW = REC_LDS_THREADS / 64;
+  const CfById better;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t n = ctl->n_lds;
+  for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) {
+    const uint32_t s = lds_list[q];
+    const uint32_t tsize = 1u << tlg[s], mask = tsize - 1;    // (<= REC_LDS_SLOTS here)
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    for (uint32_t i = tid; i < tsize; i += REC_LDS_THREADS) { s_key[i] = 0; s_sq[i] = 0.0; s_sum[i] = 0.0; }
+    __syncthreads();
+    for (uint32_t i = tid; i < L; i += REC_LDS_THREADS) {          // the session's items: excluded, first positions
+      const uint32_t a = items[b0 + i];
+      if (a == 0) continue;
+      bool claimed;
+      const uint32_t h = rec_slot<true>(s_key, mask, a, &claimed);
+      s_sq[h] = -1.0;
+      atomicMax(reinterpret_cast<uint32_t*>(&s_sum[h]), rec_first_word(i));
+    }
+    __syncthreads();
+    bool seen0 = false;                                             // (item 0 is never a key: its duplicates are told here)
+    for (uint32_t i = 0; i < L; i++) {                              // session order; everything up to the scan is uniform
+      const uint32_t a = items[b0 + i];
+      if (a == 0) {
+        if (seen0) continue;
+        seen0 = true;
+      } else if (rec_low_word(&s_sum[rec_find(s_key, mask, a)]) != rec_first_word(i)) {
+        continue;                                                   // a later occurrence
+      }
+      uint4 sn;
+      if (!dir_find(dir, dmask, a, &sn) || sn.z == 0) continue;
+      bool dummy = false;
+      const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+      const uint32_t size = 1u << meta_lg(sn.x);
+      const uint64_t* cells = row_cells(arena, sn.z);
+      for (uint32_t p = tid; p < size; p += REC_LDS_THREADS) {
+        const uint64_t c = cells[p];
+        const uint32_t b = cell_key(c);
+        if (b == 0) continue;                                       // an empty cell, or column 0 (the totals)
+        bool claimed;
+        const uint32_t h = rec_slot<true>(s_key, mask, b, &claimed);
+        double sqb;
+        if (claimed) {
+          sqb = rec_sqrt_total(dir, dmask, arena, b);
+          s_sq[h] = sqb;
+        } else {
+          sqb = s_sq[h];
+          if (sqb < 0.0) continue;                                  // an item of the session
+          if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);   // claimed by another lane of this row (a twice-held key)
+        }
+        __hip_atomic_fetch_add(&s_sum[h], rec_term(cell_val(c), sa, sqb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      __syncthreads();
+    }
+    __syncthreads();
+    // the k best: every wave over its 64-slot steps (k_cf_topk's loop), then wave 0 merges the waves' lists
+    CfCand top{NONE, 0xffffffffu, 0xffffffffu};
+    for (uint32_t p0 = w * 64; p0 < tsize; p0 += REC_LDS_THREADS) {
+      const uint32_t p = p0 + lane;
+      const uint32_t b = s_key[p];
+      CfCand cand{NONE, 0xffffffffu, b};
+      if (b != 0 && s_sq[p] > 0.0) cand.key = __double_as_longlong(s_sum[p]);
+      const CfCand kth = cf_shfl(top, (int)k - 1);
+      if (!__any(cand.key != NONE && better(cand, kth))) continue;
+      cf_sort64<CfById>(cand, lane);
+      const CfCand rev = cf_shfl(cand, 63 - (int)lane);
+      if (better(rev, top)) top = rev;
+      cf_merge_stages<CfById>(top, lane, 32);
+    }
+    __syncthreads();                                                // the table is read: its first words hold the lists
+    long long* l_key = reinterpret_cast<long long*>(s_sq);
+    l_key[w * 64 + lane] = top.key;
+    s_key[w * 64 + lane] = top.id;
+    __syncthreads();
+    if (w == 0) {
+      for (uint32_t v = 1; v < NW; v++) {
+        const CfCand o{l_key[v * 64 + 63 - lane], 0xffffffffu, s_key[v * 64 + 63 - lane]};
+        if (better(o, top)) top = o;
+        cf_merge_stages<CfById>(top, lane, 32);
+      }
+      const bool have = lane < k && top.key != NONE;
+      if (have) {
+        ids[(uint64_t)s * k + lane] = top.id;
+        scores[(uint64_t)s * k + lane] = __longlong_as_double(top.key);
+      }
+      const uint64_t m = __ballot(have);
+      if (lane == 0) counts[s] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();                                                // before the next session clears the table
+  }
+}
+
+// ---- global tier -----------------------------------------------------------------------------------------------------------
+// Sessions are processed in GROUPS by their table offset (big_off / G): group g's tables live at big_off - g * G in the
+// buffers gk (keys), gq (sqrt of the totals, -1: an item), gs (sums), which the host has zeroed.  owner[segment] = the session
+// index (in big_list) whose table holds the segment; zpos[idx] = 2^32-1 - the first position of item 0 in the session.
+struct RecGl {
+  uint32_t* gk;
+  double* gq;
+  double* gs;
+  uint32_t* owner;
+  uint32_t* zpos;
+  const uint32_t* big_list;
+  const unsigned long long* big_off;
+  const uint8_t* tlg;
+  uint32_t n_big;
+  uint32_t g;
+  unsigned long long G;
+};
+
+__device__ __forceinline__ bool rec_in_group(const RecGl& R, uint32_t idx, uint64_t* loc) {
+  const uint64_t o = R.big_off[idx];
+  if (o / R.G != R.g) return false;
+  *loc = o - (uint64_t)R.g * R.G;
+  return true;
+}
+
+// a workgroup per session: the items as excluded keys, item 0's first position, the owners of the table's segments
+__global__ __launch_bounds__(256) void k_rec_gl_init(RecGl R, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items) {
+  for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
+    uint64_t loc;
+    if (!rec_in_group(R, idx, &loc)) continue;
+    const uint32_t s = R.big_list[idx];
+    const uint64_t tsize = 1ull << R.tlg[s], b0 = off[s], L = off[s + 1] - b0;
+    for (uint64_t j = threadIdx.x; j < tsize / REC_SEG; j += blockDim.x) R.owner[loc / REC_SEG + j] = idx;
+    uint32_t* keys = R.gk + loc;
+    for (uint64_t i = threadIdx.x; i < L; i += blockDim.x) {
+      const uint32_t a = items[b0 + i];
+      if (a == 0) { atomicMax(&R.zpos[idx], rec_first_word(i)); continue; }
+      bool claimed;
+      const uint32_t h = rec_slot<false>(keys, (uint32_t)(tsize - 1), a, &claimed);
+      R.gq[loc + h] = -1.0;
+      atomicMax(reinterpret_cast<uint32_t*>(&R.gs[loc + h]), rec_first_word(i));
+    }
+  }
+}
+
+// per (position p0 + j, session idx) with j < np: the 512-cell chunks of the row of the session's item there, 0 for a later
+// occurrence, an item without a row, a session of this length or less, a session of another group
+__global__ __launch_bounds__(256) void k_rec_gl_plan(RecGl R, DirSlot* dir, uint32_t dmask, const uint64_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ items, uint32_t p0, uint32_t np, uint32_t* cnt) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (uint64_t)np * R.n_big) return;
+  const uint32_t idx = (uint32_t)(t % R.n_big), p = p0 + (uint32_t)(t / R.n_big);
+  uint32_t c = 0;
+  uint64_t loc;
+  if (rec_in_group(R, idx, &loc)) {
+    const uint32_t s = R.big_list[idx];
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    if (p < L) {
+      const uint32_t a = items[b0 + p];
+      const uint32_t mask = (uint32_t)((1ull << R.tlg[s]) - 1u);   // (tables of 2^32 slots: mask 2^32 - 1)
+      const bool first = a == 0 ? R.zpos[idx] == rec_first_word(p)
+                                : rec_low_word(&R.gs[loc + rec_find(R.gk + loc, mask, a)]) == rec_first_word(p);
+      uint4 sn;
+      if (first && dir_find(dir, dmask, a, &sn) && sn.z != 0) c = ((1u << meta_lg(sn.x)) + REC_CHUNK - 1) / REC_CHUNK;
+    }
+  }
+  cnt[t] = c;
+}
+
+// position p = p0 + j: a wave per chunk task; scan[j * n_big + idx] = the first task of session idx (scan of k_rec_gl_plan's counts)
+__global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
+                                                     const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
+                                                     uint32_t j, const uint64_t* __restrict__ scan) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint64_t* sc = scan + (uint64_t)j * R.n_big;
+  const uint64_t t0 = sc[0], t1 = sc[R.n_big];
+  for (uint64_t t = t0 + wave; t < t1; t += nwaves) {
+    uint32_t lo = 0, hi = R.n_big;                                  // the last session whose first task is <= t
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sc[mid] <= t) lo = mid; else hi = mid; }
+    const uint32_t idx = lo;
+    const uint64_t chunk = t - sc[idx];
+    const uint64_t loc = R.big_off[idx] - (uint64_t)R.g * R.G;
+    const uint32_t s = R.big_list[idx];
+    const uint32_t mask = (uint32_t)((1ull << R.tlg[s]) - 1u);   // (tables of 2^32 slots: mask 2^32 - 1)
+    const uint32_t a = items[off[s] + p0 + j];
+    uint4 sn;
+    dir_find(dir, dmask, a, &sn);                                   // (there: the plan gave it chunks)
+    bool dummy = false;
+    const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+    const uint32_t size = 1u << meta_lg(sn.x);
+    const uint64_t* cells = row_cells(arena, sn.z);
+    uint32_t* keys = R.gk + loc;
+    double* sq = R.gq + loc;
+    double* sum = R.gs + loc;
+    uint64_t cv[REC_CHUNK / 64];
+#pragma unroll
+    for (uint32_t u = 0; u < REC_CHUNK / 64; u++) {                 // the chunk's loads all in flight
+      const uint64_t p = chunk * REC_CHUNK + u * 64 + lane;
+      cv[u] = p < size ? cells[p] : 0ull;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < REC_CHUNK / 64; u++) {
+      const uint32_t b = cell_key(cv[u]);
+      if (b == 0) continue;
+      bool claimed;
+      const uint32_t h = rec_slot<false>(keys, mask, b, &claimed);
+      double sqb;
+      if (claimed) {
+        sqb = rec_sqrt_total(dir, dmask, arena, b);
+        sq[h] = sqb;
+      } else {
+        sqb = __hip_atomic_load(&sq[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sqb < 0.0) continue;
+        if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);
+      }
+      unsafeAtomicAdd(&sum[h], rec_term(cell_val(cv[u]), sa, sqb));
+    }
+  }
+}
+
+// a wave per REC_SEG-slot segment of the group's tables: its 64 best -> lk / li (64 entries per segment, best first)
+__global__ __launch_bounds__(256) void k_rec_gl_topk(RecGl R, uint64_t nseg, uint32_t k, long long* __restrict__ lk,
+                                                     uint32_t* __restrict__ li) {
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  const CfById better;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  for (uint64_t g = wave; g < nseg; g += nwaves) {
+    if (R.owner[g] == 0xffffffffu) continue;
+    CfCand top{NONE, 0xffffffffu, 0xffffffffu};
+    for (uint64_t p0 = g * REC_SEG; p0 < (g + 1) * REC_SEG; p0 += 64) {
+      const uint64_t p = p0 + lane;
+      const uint32_t b = R.gk[p];
+      CfCand cand{NONE, 0xffffffffu, b};
+      if (b != 0 && R.gq[p] > 0.0) cand.key = __double_as_longlong(R.gs[p]);
+      const CfCand kth = cf_shfl(top, (int)k - 1);
+      if (!__any(cand.key != NONE && better(cand, kth))) continue;
+      cf_sort64<CfById>(cand, lane);
+      const CfCand rev = cf_shfl(cand, 63 - (int)lane);
+      if (better(rev, top)) top = rev;
+      cf_merge_stages<CfById>(top, lane, 32);
+    }
+    lk[g * 64 + lane] = top.key;
+    li[g * 64 + lane] = top.id;
+  }
+}
+
+// a workgroup per session of the group: its segments' lists merged (each wave a share, then wave 0 over the waves), the k best out
+__global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_merge(RecGl R, uint32_t k, const long long* __restrict__ lk,
+                                                                    const uint32_t* __restrict__ li, uint32_t* __restrict__ ids,
+                                                                    double* __restrict__ scores, uint32_t* __restrict__ counts) {
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  constexpr uint32_t NW = REC_MERGE_THREADS / 64;
+  __shared__ long long m_key[NW * 64];
+  __shared__ uint32_t m_id[NW * 64];
+  const CfById better;
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
+    uint64_t loc;
+    if (!rec_in_group(R, idx, &loc)) continue;
+    const uint32_t s = R.big_list[idx];
+    const uint64_t g0 = loc / REC_SEG, ns = (1ull << R.tlg[s]) / REC_SEG;
+    CfCand top{NONE, 0xffffffffu, 0xffffffffu};
+    for (uint64_t g = g0 + w; g < g0 + ns; g += NW) {
+      const CfCand o{lk[g * 64 + 63 - lane], 0xffffffffu, li[g * 64 + 63 - lane]};
+      if (better(o, top)) top = o;
+      cf_merge_stages<CfById>(top, lane, 32);
+    }
+    m_key[w * 64 + lane] = top.key;
+    m_id[w * 64 + lane] = top.id;
+    __syncthreads();
+    if (w == 0) {
+      for (uint32_t v = 1; v < NW; v++) {
+        const CfCand o{m_key[v * 64 + 63 - lane], 0xffffffffu, m_id[v * 64 + 63 - lane]};
+        if (better(o, top)) top = o;
+        cf_merge_stages<CfById>(top, lane, 32);
+      }
+      const bool have = lane < k && top.key != NONE;
+      if (have) {
+        ids[(uint64_t)s * k + lane] = top.id;
+        scores[(uint64_t)s * k + lane] = __longlong_as_double(top.key);
+      }
+      const uint64_t m = __ballot(have);
+      if (lane == 0) counts[s] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+  }
+}

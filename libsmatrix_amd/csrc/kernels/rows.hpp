@@ -355,6 +355,10 @@ struct CfCand {
 __device__ __forceinline__ bool cf_better(const CfCand& a, const CfCand& b) {
   return a.key > b.key || (a.key == b.key && a.slot < b.slot);
 }
+// the order of the sort and merge below: (score desc, slot asc) for k_cf_topk, (score desc, id asc) for kernels/recommend.hpp
+struct CfBySlot {
+  __device__ __forceinline__ bool operator()(const CfCand& a, const CfCand& b) const { return cf_better(a, b); }
+};
 __device__ __forceinline__ CfCand cf_shfl_xor(const CfCand& v, int j) {
   CfCand o;
   o.key = ((long long)__shfl_xor((int)(v.key >> 32), j) << 32) | (uint32_t)__shfl_xor((int)v.key, j);
@@ -370,20 +374,24 @@ __device__ __forceinline__ CfCand cf_shfl(const CfCand& v, int src) {
   return o;
 }
 // stages j = from, from/2, .. 1 of a bitonic network over the wave's 64 lanes, best first
+template <typename Better = CfBySlot>
 __device__ __forceinline__ void cf_merge_stages(CfCand& v, uint32_t lane, uint32_t from) {
+  const Better better;
   for (uint32_t j = from; j; j >>= 1) {
     const CfCand o = cf_shfl_xor(v, (int)j);
     const bool want_better = (lane & j) == 0;              // the lower lane of a pair keeps the better one
-    if (cf_better(o, v) == want_better) v = o;
+    if (better(o, v) == want_better) v = o;
   }
 }
+template <typename Better = CfBySlot>
 __device__ __forceinline__ void cf_sort64(CfCand& v, uint32_t lane) {
+  const Better better;
   for (uint32_t k2 = 2; k2 <= 64; k2 <<= 1) {
     for (uint32_t j = k2 >> 1; j; j >>= 1) {
       const CfCand o = cf_shfl_xor(v, (int)j);
       const bool down = (lane & k2) == 0 || k2 == 64;     // blocks alternate direction; the last pass is best-first
       const bool want_better = ((lane & j) == 0) == down;
-      if (cf_better(o, v) == want_better) v = o;
+      if (better(o, v) == want_better) v = o;
     }
   }
 }

@@ -1,0 +1,188 @@
+// smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev), host side.
+// Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
+// u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
+//
+// Under the matrix lock, after the scalar mirror has been written back (cache_sync):
+//   1. k_rec_bound sorts the sessions into the LDS tier and the global tier; ONE read-back of RecCtl (counts, global-tier sizes)
+//   2. k_rec_lds: every LDS-tier session, one workgroup each
+//   3. the global tier, per group of sessions whose tables fit REC_GROUP_SLOTS (normally one group): zeroed tables, k_rec_gl_init,
+//      per block of item positions the chunk counts (k_rec_gl_plan) and their scan, a k_rec_gl_scan launch per position (the
+//      kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
+
+namespace {
+
+constexpr uint64_t REC_GROUP_SLOTS = 1ull << 25;      // global-tier tables per group: 640 MB (20 bytes a slot), plus the largest table
+constexpr uint64_t REC_PLAN_MAX = 1ull << 24;         // (position, session) counts per plan
+
+struct RecScratch {
+  DevBuf<RecCtl> ctl;
+  DevBuf<uint32_t> lds_list, big_list, gk, owner, zpos, cnt, li;
+  DevBuf<unsigned long long> big_off;
+  DevBuf<uint8_t> tlg;
+  DevBuf<double> gq, gs;
+  DevBuf<long long> lk;
+  DevBuf<uint64_t> scan, part;
+  DevBuf<uint32_t> h_items, h_ids, h_counts;         // the host flavour's device copies of the caller's arrays
+  DevBuf<uint64_t> h_off;
+  DevBuf<double> h_scores;
+  hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
+};
+
+RecScratch& rec_of(Matrix* m) {
+  if (!m->rec) m->rec = new RecScratch();
+  return *static_cast<RecScratch*>(m->rec);
+}
+
+template <typename T>
+bool rec_big(const DevBuf<T>& b) { return b.cap * sizeof(T) > ((size_t)64 << 20); }
+template <typename T>
+void rec_trim(DevBuf<T>& b, bool all) {
+  if (all || rec_big(b)) b.release();                                 // (as the export: no HBM pinned for good)
+}
+void rec_trim_all(RecScratch& x, bool all) {
+  rec_trim(x.ctl, all); rec_trim(x.lds_list, all); rec_trim(x.big_list, all); rec_trim(x.gk, all); rec_trim(x.owner, all);
+  rec_trim(x.zpos, all); rec_trim(x.cnt, all); rec_trim(x.li, all); rec_trim(x.big_off, all); rec_trim(x.tlg, all); rec_trim(x.gq, all);
+  rec_trim(x.gs, all); rec_trim(x.lk, all); rec_trim(x.scan, all); rec_trim(x.part, all); rec_trim(x.h_items, all); rec_trim(x.h_ids, all);
+  rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all);
+}
+
+bool rec_any_big(const RecScratch& x) {
+  return rec_big(x.lds_list) || rec_big(x.big_list) || rec_big(x.gk) || rec_big(x.owner) || rec_big(x.zpos) || rec_big(x.cnt) ||
+         rec_big(x.li) || rec_big(x.big_off) || rec_big(x.tlg) || rec_big(x.gq) || rec_big(x.gs) || rec_big(x.lk) || rec_big(x.scan) ||
+         rec_big(x.part);
+}
+
+// The scratch is the matrix's, the stream the caller's: a call on another stream than the one before it (or the host flavour,
+// on the matrix's stream) must not touch the scratch while kernels of the earlier call may still read it.
+void rec_begin(RecScratch& x, hipStream_t s) {
+  if (x.done) HIP_OK(hipStreamWaitEvent(s, x.done, 0));
+}
+void rec_end(RecScratch& x, hipStream_t s) {
+  if (!x.done) HIP_OK(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(x.done, s));
+}
+
+// out[0 .. n] = exclusive prefix of n u32 counts (the export's scan kernels)
+void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint64_t* out) {
+  const uint32_t nt = (uint32_t)((n + EX_TILE - 1) / EX_TILE);
+  x.part.need((size_t)nt + 1);
+  if (nt) hipLaunchKernelGGL(k_ex_scan_reduce, dim3(nt), dim3(EX_THREADS), 0, s, in, n, x.part.p);
+  hipLaunchKernelGGL(k_ex_scan_part, dim3(1), dim3(EX_THREADS), 0, s, x.part.p, nt);
+  hipLaunchKernelGGL(k_ex_scan_apply, dim3(std::max<uint32_t>(nt, 1)), dim3(EX_THREADS), 0, s, in, n, x.part.p, nt, out);
+  HIP_OK(hipGetLastError());
+}
+
+// the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back)
+void rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
+             uint32_t* d_ids, double* d_scores, uint32_t* d_counts) {
+  DirSlot* dir = m->d_dir;
+  const uint32_t dmask = m->dir_size - 1;
+  x.ctl.need(1); x.lds_list.need(n); x.big_list.need(n); x.big_off.need(n); x.tlg.need(n);
+  HIP_OK(hipMemsetAsync(x.ctl.p, 0, sizeof(RecCtl), s));
+  hipLaunchKernelGGL(k_rec_bound, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, d_off,
+                     d_items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, d_counts);
+  HIP_OK(hipGetLastError());
+  RecCtl c;
+  HIP_OK(hipMemcpyAsync(&c, x.ctl.p, sizeof c, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (c.n_lds)
+    hipLaunchKernelGGL(k_rec_lds, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
+                       x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts);
+  HIP_OK(hipGetLastError());
+  if (!c.n_big) return;
+  const uint64_t ngroups = (c.total_slots + REC_GROUP_SLOTS - 1) / REC_GROUP_SLOTS;
+  const uint64_t cap = ngroups == 1 ? c.total_slots : REC_GROUP_SLOTS + c.max_slots;
+  const uint64_t nseg = cap / REC_SEG;
+  const uint32_t np = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.max_len, REC_PLAN_MAX / c.n_big));
+  x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big); x.lk.need(nseg * 64); x.li.need(nseg * 64);
+  x.cnt.need((uint64_t)np * c.n_big); x.scan.need((uint64_t)np * c.n_big + 1);
+  RecGl R{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
+  for (uint64_t g = 0; g < ngroups; g++) {
+    R.g = (uint32_t)g;
+    const uint64_t ext = ngroups == 1 ? cap : std::min<uint64_t>(cap, c.total_slots - g * REC_GROUP_SLOTS + c.max_slots);
+    HIP_OK(hipMemsetAsync(x.gk.p, 0, ext * 4, s));
+    HIP_OK(hipMemsetAsync(x.gq.p, 0, ext * 8, s));
+    HIP_OK(hipMemsetAsync(x.gs.p, 0, ext * 8, s));
+    HIP_OK(hipMemsetAsync(x.owner.p, 0xff, nseg * 4, s));
+    HIP_OK(hipMemsetAsync(x.zpos.p, 0, (size_t)c.n_big * 4, s));
+    hipLaunchKernelGGL(k_rec_gl_init, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, R, d_off, d_items);
+    HIP_OK(hipGetLastError());
+    for (uint32_t p0 = 0; p0 < c.max_len; p0 += np) {
+      const uint32_t nj = std::min<uint32_t>(np, c.max_len - p0);
+      const uint64_t nt = (uint64_t)nj * c.n_big;
+      hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, R, dir, dmask, d_off, d_items, p0, nj, x.cnt.p);
+      HIP_OK(hipGetLastError());
+      rec_scan(x, s, x.cnt.p, nt, x.scan.p);
+      for (uint32_t j = 0; j < nj; j++)
+        hipLaunchKernelGGL(k_rec_gl_scan, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off, d_items, p0, j, x.scan.p);
+      HIP_OK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, R, nseg, k, x.lk.p,
+                       x.li.p);
+    hipLaunchKernelGGL(k_rec_gl_merge, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, R, k, x.lk.p, x.li.p,
+                       d_ids, d_scores, d_counts);
+    HIP_OK(hipGetLastError());
+  }
+}
+
+void recommend_release(Matrix* m) {
+  if (!m->rec) return;
+  RecScratch* x = static_cast<RecScratch*>(m->rec);
+  if (x->done) { HIP_OK(hipEventSynchronize(x->done)); (void)hipEventDestroy(x->done); }
+  rec_trim_all(*x, true);
+  delete static_cast<RecScratch*>(m->rec);
+  m->rec = nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, uint32_t k,
+                                   uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream) {
+  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return -1;
+  if (n_sessions == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  rec_run(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts);
+  rec_end(x, s);
+  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
+  rec_trim_all(x, false);
+  return 0;
+}
+
+int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, uint32_t k,
+                               uint32_t* ids, double* scores, uint32_t* counts) {
+  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return -1;
+  if (n_sessions == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = m->stream;
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
+  std::vector<uint64_t> rel(n + 1);
+  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
+  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
+  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as cf_topk_batch's
+  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
+  rec_run(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p);
+  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
+  rec_end(x, s);
+  HIP_OK(hipStreamSynchronize(s));
+  rec_trim_all(x, false);
+  return 0;
+}
+
+}  // extern "C"

@@ -25,6 +25,20 @@ def _export_order(order):
     return _EXPORT_ORDERS[order]
 
 
+def _sessions(sessions):
+    """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
+    lens = np.array([len(s) for s in sessions], dtype=np.uint64)
+    offsets = np.zeros(len(sessions) + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    ids = _u32(np.concatenate([np.asarray(s, dtype=np.uint32) for s in sessions]) if len(sessions) else np.zeros(0, np.uint32))
+    return offsets, ids
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be 1..64, not %r" % (k,))
+
+
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
@@ -177,13 +191,34 @@ class SparseMatrix:
     def cf_topk_batch_dev(self, n, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, stream=None):
         self._lib.smatrix_cf_topk_batch_dev(self._h, n, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, stream)
 
+    def cf_recommend_batch(self, sessions, k):
+        """session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch): every session is a sequence of
+        item ids; its k <= 64 best candidates over its items' rows, by the sum of their cosines, its own items and id 0 left
+        out: -> (ids[n,k], scores[n,k] float64, counts[n]); best first, equal scores by ascending id"""
+        _check_k(k)
+        offsets, items = _sessions(sessions)
+        n = len(sessions)
+        ids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_batch(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), k,
+                                                      ids.ctypes.data_as(_lib.u32p),
+                                                      scores.ctypes.data_as(C.POINTER(C.c_double)), _p(counts)) != 0:
+            raise ValueError("smatrix_cf_recommend_batch: k must be 1..64 and n_sessions < 2^32")
+        return ids, scores, counts
+
+    def cf_recommend_batch_dev(self, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, stream=None):
+        """the same on device arrays (raw pointers): offsets uint64[n+1], items uint32, ids uint32[n*k], scores float64[n*k],
+        counts uint32[n].  stream: a torch.cuda.Stream or a hipStream_t as int (None: the legacy default stream, synchronised)"""
+        _check_k(k)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
+
     def cf_import_sessions(self, sessions):
         """CF-recommender write path (examples/cf_recommender.c:36-47): every session is a sequence of item ids; all
         their L*L incr ops are generated and applied on the GPU"""
-        lens = np.array([len(s) for s in sessions], dtype=np.uint64)
-        offsets = np.zeros(len(sessions) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offsets[1:])
-        ids = _u32(np.concatenate([np.asarray(s, dtype=np.uint32) for s in sessions]) if len(sessions) else np.zeros(0, np.uint32))
+        offsets, ids = _sessions(sessions)
         if self._lib.smatrix_cf_import_sessions(self._h, len(sessions), offsets.ctypes.data_as(_lib.u64p), _p(ids)) != 0:
             raise ValueError("smatrix_cf_import_sessions")
 
