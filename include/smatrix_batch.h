@@ -156,6 +156,44 @@ int smatrix_export_dev(smatrix_t* self, int order, uint64_t cap_rows, uint64_t c
                        uint32_t* d_rows, uint64_t* d_row_ptr, uint32_t* d_pairs,
                        uint64_t* n_rows, uint64_t* nnz, void* hip_stream);
 
+/* ---- merge of two matrices, CSR import ------------------------------------- */
+/* smatrix_merge:       dst[x,y]  op=  src[x,y]  for every pair of src; op is SMATRIX_OP_SET, _INCR or _DECR
+ *                      (total += part; a sliding window: total += today, total -= day_30).
+ * smatrix_import_csr:  the same with the pairs taken from a CSR in smatrix_export's layout (rows[n_rows], row_ptr[n_rows + 1],
+ *                      pairs = {column, value} interleaved): the inverse of smatrix_export.
+ * Which ops: merge applies op(x, y, v) once for every pair (y, v) that smatrix_export(src, TABLE) lists under row x -- every
+ *   non-empty slot, value-0 cells with a non-zero key included (an incr by 0 creates the cell, as in the reference).  A source
+ *   row without pairs (quirk Q3) contributes nothing and is not created in dst.  import_csr applies one op per pair of the CSR;
+ *   a row id may occur more than once in rows, and a column more than once in a row.
+ * Result: the batch contract at the top of this file for the whole call as if it were ONE batch: the final state is what the
+ *   reference reaches by applying those ops one by one in some order; values are exact (uint32, wrapping); row sizes and `used`
+ *   are the reference's.  SET with a key that occurs more than once in the CSR: the LAST occurrence (highest position in pairs)
+ *   wins, also when the occurrences fall into different internal batches.  Nothing beyond the batch contract is promised for
+ *   the layout of a row's table.
+ * Bounded scratch: the work runs in internal batches of at most max(max_batch, longest source row) ops -- max_batch == 0: 2^24,
+ *   the batch size the write path is tuned for; above 2^31: 2^31 -- (import_csr: of exactly max_batch pairs, rows are split).
+ *   Device memory taken beyond the matrices is proportional to that bound plus 20 bytes per source ROW (import_csr host flavour:
+ *   12 per row), never to the number of pairs: no whole-matrix CSR, no triples.  The result does not depend on max_batch in
+ *   anything the contract fixes (values, row set, sizes, `used`).
+ * *n_ops (may be NULL) receives the number of ops applied.  Returns 0; -1 and nothing changed for: an op other than SET / INCR /
+ *   DECR, dst == src, the two matrices on different devices, a CSR whose row_ptr is not non-decreasing from 0 (checked on the
+ *   device before the first write).
+ * Locks and mirrors: merge holds both matrices' locks for the call, taken in one global order (merge(a, b) and merge(b, a) on
+ *   two threads cannot deadlock); it takes no file lock, so the file-then-matrix order of smatrix_flush holds.  Scalar writes
+ *   still in src's and dst's host mirrors are written back first (as smatrix_export does) and dst's mirror is dropped.
+ *   File-backed dst and src work unchanged: the rows dst changed are DIRTY and reach its file by the usual flush;
+ *   smatrix_stats_t::batches counts the internal batches, and a call during which SMATRIX_FLUSH_EVERY falls due takes ONE
+ *   checkpoint, at its end.  src is not modified.
+ * merge and the host flavour of import_csr run on the matrix's own stream and return when done.  _dev: arrays in device memory
+ *   on the matrix's GPU, work ordered after hip_stream's earlier work and complete on it when the call returns (NULL = the
+ *   legacy default stream). */
+int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops);
+int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr,
+                       const uint32_t* pairs, uint64_t max_batch, uint64_t* n_ops);
+int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows,
+                           const uint64_t* d_row_ptr, const uint32_t* d_pairs, uint64_t max_batch,
+                           uint64_t* n_ops, void* hip_stream);
+
 /* Capacity hint, like vector::reserve: map at least `bytes` of device memory for row tables now instead of in growth
  * steps later (each step is a call into the driver, normally ~0.3 ms, but one that can block for seconds while the driver
  * still has freed memory to wipe).  Nothing observable changes.  Returns 0. */

@@ -77,6 +77,9 @@ def load():
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
         "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),
         "smatrix_export_dev": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, V, V, V, u64p, u64p, V]),
+        "smatrix_merge": (C.c_int, [H, H, C.c_int, C.c_uint64, u64p]),
+        "smatrix_import_csr": (C.c_int, [H, C.c_int, C.c_uint64, u32p, u64p, u32p, C.c_uint64, u64p]),
+        "smatrix_import_csr_dev": (C.c_int, [H, C.c_int, C.c_uint64, V, V, V, C.c_uint64, u64p, V]),
         "smatrix_stats": (None, [H, C.POINTER(Stats)]),
         "smatrix_stats_sz": (None, [H, C.POINTER(Stats), C.c_size_t]),
         "smatrix_profile": (None, [H, C.c_int]),

@@ -1,0 +1,180 @@
+// kernels/merge.hpp -- record emission for smatrix_merge / smatrix_import_csr (include/smatrix_batch.h): row tables, or a CSR,
+// straight into a bounded batch of packed {x, key, value} records -- the form the write path takes with in_stride == 3
+// (smatrix_apply_packed_dev).  No whole-matrix CSR and no triples of nnz words in between.
+// A fragment of smx_kernels.hpp: included there, after export.hpp, INSIDE namespace smx; not a header of its own.
+//
+// From row tables (one internal batch = the rows [r0, r1) of the export's row list, `items`, whose exact pair counts were scanned
+// into ptr[] by k_ex_count / k_ex_scan_*): the record of a row's j-th non-empty cell, in slot order, is number
+// ptr[r] - ptr[r0] + j of the batch.
+//   k_mg_emit          a wave per row of up to GETROW_WAVE_MAX cells, 128 cells (1 KiB) per step with 16-byte loads, the
+//                      non-empty ones compacted with ballots + prefix popcounts; a longer row is only noted down in `big`, one
+//                      entry {row, segment} per segment of GETROW_SEG cells (big[0] = entries)
+//   k_mg_emit_big<C>   the noted segments, a 1024-lane workgroup each (as k_getrow_big; a workgroup touches its own entries only):
+//                      <true> counts a cut row's segments, <false> writes every segment's records behind those of the segments
+//                      before it
+// Each source cell is read once (twice in a row of >= 2 segments) and 12 bytes leave per pair.
+//
+// A cut row's segment counts live in seg_cnt[] at (byte offset of the segment in the arena) >> 18: a segment is 256 KiB of
+// cells and rows do not overlap, so no two segments of any two rows share an index, and the array is arena / 65536 bytes -- no
+// plan pass that numbers the segments.
+
+constexpr uint32_t MG_SEG_SHIFT = 18;                       // log2(GETROW_SEG cells * 8 bytes)
+static_assert((1u << MG_SEG_SHIFT) == GETROW_SEG * 8, "a segment of the merge is a segment of getrow");
+
+__device__ __forceinline__ void mg_put(uint32_t* __restrict__ rec, uint64_t at, uint32_t x, uint32_t key, uint32_t val) {
+  uint32_t* p = rec + 3 * at;
+  p[0] = x; p[1] = key; p[2] = val;
+}
+
+__global__ __launch_bounds__(256) void k_mg_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                 const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                 uint32_t* __restrict__ rec, uint32_t* big) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  const uint64_t lt = (1ull << lane) - 1;
+  const uint64_t base = ptr[r0];
+  for (uint32_t r = r0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); r < r1; r += nwaves) {
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    if (s.z == 0) continue;                                            // no block yet (quirk Q3): no pairs
+    const uint32_t size = 1u << meta_lg(s.x);
+    if (size > GETROW_WAVE_MAX) {                                      // one entry {row, segment} per segment, in any order
+      const uint32_t nseg = getrow_nseg(size);
+      uint32_t e0 = 0;
+      if (lane == 0) e0 = atomicAdd(&big[0], nseg);
+      e0 = (uint32_t)__shfl((int)e0, 0);
+      for (uint32_t g = lane; g < nseg; g += 64) { big[1 + 2 * (e0 + g)] = r; big[2 + 2 * (e0 + g)] = g; }
+      continue;
+    }
+    const uint4* cells = reinterpret_cast<const uint4*>(row_cells(arena, s.z));
+    const uint32_t x = s.y;
+    uint64_t at = ptr[r] - base;
+    auto fetch = [&](uint32_t p0) -> uint4 {
+      const uint32_t p = p0 + 2 * lane;
+      return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
+    };
+    auto step = [&](const uint4 c) {                                   // compacts the 128 cells held in c (slot order)
+      const bool ne0 = (c.x | c.y) != 0, ne1 = (c.z | c.w) != 0;
+      const uint64_t m0 = __ballot(ne0), m1 = __ballot(ne1);
+      uint64_t o = at + (uint32_t)__popcll(m0 & lt) + (uint32_t)__popcll(m1 & lt);
+      if (ne0) mg_put(rec, o, x, c.x, c.y);
+      o += ne0;
+      if (ne1) mg_put(rec, o, x, c.z, c.w);
+      at += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
+    };
+    // every load of a row of up to 512 cells (the CF shape and four times that) is in flight before the first is consumed
+    const uint4 a0 = fetch(0), a1 = fetch(128), a2 = fetch(256), a3 = fetch(384);
+    step(a0);
+    if (size > 128) step(a1);
+    if (size > 256) { step(a2); step(a3); }
+    for (uint32_t p0 = 512; p0 < size; p0 += 512) {                    // (sizes are powers of two: 1024 and up here)
+      const uint4 b0 = fetch(p0), b1 = fetch(p0 + 128), b2 = fetch(p0 + 256), b3 = fetch(p0 + 384);
+      step(b0); step(b1); step(b2); step(b3);
+    }
+  }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mg_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                      const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                      const uint32_t* big, uint32_t* seg_cnt) {
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t s_written;
+  const uint32_t nent = big[0];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t lt = (1ull << lane) - 1;
+  const uint64_t base = ptr[r0];
+  auto block_sum = [&](uint32_t v) -> uint32_t {          // sum over the workgroup, to every lane
+    for (uint32_t d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    __syncthreads();
+    if (lane == 0) wsum[w] = v;
+    __syncthreads();
+    uint32_t t = 0;
+    for (uint32_t i = 0; i < 16; i++) t += wsum[i];
+    __syncthreads();
+    return t;
+  };
+  for (uint32_t t = blockIdx.x; t < nent; t += gridDim.x) {
+    const uint32_t r = big[1 + 2 * t], g = big[2 + 2 * t];
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = 1u << meta_lg(s.x);                          // > GETROW_WAVE_MAX: a multiple of 2048
+    const uint32_t nseg = getrow_nseg(size);
+    if (COUNT && nseg == 1) continue;
+    const uint8_t* cell_bytes = reinterpret_cast<const uint8_t*>(row_cells(arena, s.z));
+    const uint4* cells = reinterpret_cast<const uint4*>(cell_bytes);
+    const uint64_t first = (uint64_t)(cell_bytes - arena) >> MG_SEG_SHIFT;   // the row's first entry of seg_cnt
+    {
+      const uint32_t p_begin = nseg == 1 ? 0u : g * GETROW_SEG, p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
+      if (COUNT) {
+        uint32_t c = 0;
+        for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
+          const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+          c += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+        }
+        c = block_sum(c);
+        if (threadIdx.x == 0) seg_cnt[first + g] = c;
+        continue;
+      }
+      uint32_t before_me = 0;
+      if (nseg > 1) {
+        uint32_t mine = 0;
+        for (uint32_t i = threadIdx.x; i < g; i += 1024) mine += seg_cnt[first + i];
+        before_me = block_sum(mine);
+      }
+      if (threadIdx.x == 0) s_written = before_me;
+      __syncthreads();
+      const uint64_t off = ptr[r] - base;
+      for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
+        const uint32_t written = s_written;
+        const uint4 c = cells[(p0 >> 1) + threadIdx.x];
+        const bool ne0 = (c.x | c.y) != 0, ne1 = (c.z | c.w) != 0;
+        const uint64_t m0 = __ballot(ne0), m1 = __ballot(ne1);
+        if (lane == 0) wsum[w] = (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t i = 0; i < 16; i++) { const uint32_t v = wsum[i]; if (i < w) before += v; total += v; }
+        uint64_t o = off + written + before + (uint32_t)__popcll(m0 & lt) + (uint32_t)__popcll(m1 & lt);
+        if (ne0) mg_put(rec, o, s.y, c.x, c.y);
+        o += ne0;
+        if (ne1) mg_put(rec, o, s.y, c.z, c.w);
+        __syncthreads();
+        if (threadIdx.x == 0) s_written = written + total;
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// ---- from a CSR in smatrix_export's layout ------------------------------------------------------------------------------------
+// k_mg_csr_check: *bad |= 1 unless row_ptr[0] == 0 and row_ptr[i] <= row_ptr[i + 1] for every i < n_rows (before the first write)
+__global__ __launch_bounds__(256) void k_mg_csr_check(uint64_t n_rows, const uint64_t* __restrict__ row_ptr, uint32_t* bad) {
+  bool b = false;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += stride) b |= row_ptr[i] > row_ptr[i + 1];
+  if (blockIdx.x == 0 && threadIdx.x == 0) b |= row_ptr[0] != 0;
+  if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+}
+
+// A lane per pair of [t0, t0 + count); `pairs` points at pair t0.  The pair's row is the last r with row_ptr[r] <= t (rows of
+// length 0 share their successor's row_ptr and are never that one).  Two lanes of the workgroup search all of row_ptr for the
+// tile's first and last pair; every lane then searches between those two rows only -- one row in the common case, any number
+// of empty rows or a row longer than the tile in the others.
+__device__ inline uint64_t mg_row_of(const uint64_t* __restrict__ row_ptr, uint64_t lo, uint64_t hi, uint64_t t) {
+  while (hi - lo > 1) { const uint64_t mid = lo + ((hi - lo) >> 1); if (row_ptr[mid] <= t) lo = mid; else hi = mid; }
+  return lo;                                                           // row_ptr[lo] <= t < row_ptr[hi]
+}
+
+__global__ __launch_bounds__(256) void k_mg_emit_csr(uint64_t n_rows, const uint32_t* __restrict__ rows, const uint64_t* __restrict__ row_ptr,
+                                                     const uint32_t* __restrict__ pairs, uint64_t t0, uint32_t count,
+                                                     uint32_t* __restrict__ rec) {
+  __shared__ uint64_t s_row[2];
+  const uint32_t k0 = blockIdx.x * blockDim.x;                         // (the grid covers count exactly: k0 < count)
+  if (threadIdx.x < 2) {
+    const uint32_t k = threadIdx.x == 0 ? k0 : min(k0 + blockDim.x, count) - 1u;
+    s_row[threadIdx.x] = mg_row_of(row_ptr, 0, n_rows, t0 + k);
+  }
+  __syncthreads();
+  const uint32_t k = k0 + threadIdx.x;
+  if (k >= count) return;
+  const uint64_t r = mg_row_of(row_ptr, s_row[0], s_row[1] + 1, t0 + k);
+  mg_put(rec, k, rows[r], pairs[2 * (uint64_t)k], pairs[2 * (uint64_t)k + 1]);    // (a caller's uint32 array: 4-byte aligned is all that is known)
+}

@@ -1,0 +1,242 @@
+// smx_merge.inc -- smatrix_merge / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h), host side.
+// Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_measure and scan);
+// the device code is kernels/merge.hpp.
+//
+// Both calls are one loop over INTERNAL BATCHES of at most `bound` ops: a kernel writes batch b's packed {x, y, v} records into
+// one of two record buffers, the ordinary write path applies them (run_write with in_stride == 3 and no result array, as
+// smatrix_apply_packed_dev does), batches in order.  Batch b + 1 is emitted on a helper stream while the rounds of batch b run:
+//   helper:  emit(0)  emit(1)         emit(2)          ...        (emit(b) waits for the write of batch b - 2: same buffer)
+//   stream:           write(0)        write(1)         ...        (write(b) waits for emit(b))
+// merge: the batches are runs of rows of the source's row list (ex_measure: directory-slot order, exact pair counts, u64 scan),
+//        cut on the host from the scan; a row is never split, so bound = max(max_batch, longest row)
+// CSR:   the batches are runs of max_batch pairs, wherever the rows' borders fall
+// Device memory: two record buffers of 12 * bound bytes, the write path's own scratch for a batch of `bound` ops, and per ROW of
+// the source 8 (row list) + 4 (counts) + 8 (scan) bytes -- nothing per pair.
+
+namespace {
+
+constexpr uint64_t MG_DEFAULT_BATCH = 1ull << 24;      // the batch size the write path is tuned for
+constexpr uint64_t MG_MAX_BATCH = 1ull << 31;          // (a write batch holds fewer than 2^32 ops)
+
+struct MergeScratch {
+  DevBuf<uint32_t> rec[2], big, seg_cnt, flag, h_rows, h_pairs[2];
+  DevBuf<uint64_t> ptr, h_ptr;
+  hipStream_t e = nullptr;                               // the helper stream: emission
+  hipEvent_t ev_start = nullptr, ev_rec[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+};
+
+MergeScratch& mg_of(Matrix* m) {
+  if (!m->mg) {
+    MergeScratch* g = new MergeScratch();
+    HIP_OK(hipStreamCreateWithFlags(&g->e, hipStreamNonBlocking));
+    HIP_OK(hipEventCreateWithFlags(&g->ev_start, hipEventDisableTiming));
+    for (int i = 0; i < 2; i++) {
+      HIP_OK(hipEventCreateWithFlags(&g->ev_rec[i], hipEventDisableTiming));
+      HIP_OK(hipEventCreateWithFlags(&g->ev_done[i], hipEventDisableTiming));
+    }
+    m->mg = g;
+  }
+  return *static_cast<MergeScratch*>(m->mg);
+}
+
+void mg_trim_all(MergeScratch& g, bool all) {
+  ex_trim(g.rec[0], all); ex_trim(g.rec[1], all); ex_trim(g.big, all); ex_trim(g.seg_cnt, all); ex_trim(g.flag, all);
+  ex_trim(g.h_rows, all); ex_trim(g.h_pairs[0], all); ex_trim(g.h_pairs[1], all); ex_trim(g.ptr, all); ex_trim(g.h_ptr, all);
+}
+
+void merge_release(Matrix* m) {
+  if (!m->mg) return;
+  MergeScratch* g = static_cast<MergeScratch*>(m->mg);
+  mg_trim_all(*g, true);
+  (void)hipEventDestroy(g->ev_start);
+  for (int i = 0; i < 2; i++) { (void)hipEventDestroy(g->ev_rec[i]); (void)hipEventDestroy(g->ev_done[i]); }
+  (void)hipStreamDestroy(g->e);
+  delete g;
+  m->mg = nullptr;
+}
+
+bool mg_op_ok(int op) { return op == OP_SET || op == OP_INCR || op == OP_DECR; }
+uint64_t mg_batch(uint64_t max_batch) { return max_batch == 0 ? MG_DEFAULT_BATCH : std::min(max_batch, MG_MAX_BATCH); }
+
+// The loop above.  count(b) = ops of batch b (> 0); emit(b, rec, e) enqueues the kernels that write them on stream e.
+// Caller holds d->mu and has dropped d's scalar mirror; `bound` >= every count(b).
+template <typename Count, typename Emit>
+void mg_run(smatrix_t* dst, MergeScratch& g, int op, hipStream_t s, size_t nb, uint64_t bound, Count count, Emit emit) {
+  if (!nb) return;
+  Matrix* d = M(dst);
+  g.rec[0].need(3 * bound);
+  if (nb > 1) g.rec[1].need(3 * bound);
+  HIP_OK(hipEventRecord(g.ev_start, s));                  // (the caller's arrays may be the work of earlier kernels on s)
+  HIP_OK(hipStreamWaitEvent(g.e, g.ev_start, 0));
+  // smatrix_profile(dst, 1): the emission of every batch is timed with HIP events on the helper stream; one stderr line per call
+  const bool timed = d->profile;
+  std::vector<hipEvent_t> tev;
+  auto enqueue = [&](size_t b) {
+    if (b >= 2) HIP_OK(hipStreamWaitEvent(g.e, g.ev_done[b & 1], 0));
+    if (timed) { tev.emplace_back(); HIP_OK(hipEventCreate(&tev.back())); HIP_OK(hipEventRecord(tev.back(), g.e)); }
+    emit(b, g.rec[b & 1].p, g.e);
+    HIP_OK(hipGetLastError());
+    if (timed) { tev.emplace_back(); HIP_OK(hipEventCreate(&tev.back())); HIP_OK(hipEventRecord(tev.back(), g.e)); }
+    HIP_OK(hipEventRecord(g.ev_rec[b & 1], g.e));
+  };
+  enqueue(0);
+  for (size_t b = 0; b < nb; b++) {
+    if (b + 1 < nb) enqueue(b + 1);
+    HIP_OK(hipStreamWaitEvent(s, g.ev_rec[b & 1], 0));
+    const uint32_t n = count(b);
+    const uint32_t* rec = g.rec[b & 1].p;
+    d->in_stride = 3;
+    d->so.need(n);
+    d->no_ret = true;                                     // no result array: a column-0 cell takes one 64-bit add
+    apply_dev_locked(dst, op, n, rec, rec + 1, rec + 2, d->so.p, s);
+    d->no_ret = false;
+    d->in_stride = 1;
+    HIP_OK(hipEventRecord(g.ev_done[b & 1], s));
+  }
+  // (smatrix_stats_t::batches counts the internal batches -- each is a write batch the device executed; SMATRIX_FLUSH_EVERY: the
+  //  call owes ONE checkpoint when any of them was an N-th, apply_dev_locked's ckpt_due, taken by the caller's CkptAfter)
+  HIP_OK(hipStreamSynchronize(g.e));
+  if (timed) {
+    double ms = 0;
+    for (size_t i = 0; i + 1 < tev.size(); i += 2) { float t = 0; HIP_OK(hipEventElapsedTime(&t, tev[i], tev[i + 1])); ms += t; }
+    for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
+    fprintf(stderr, "[smatrix] merge: %zu internal batches of at most %llu ops, record emission %.3f ms in all (helper stream, beside the write path)\n",
+            nb, (unsigned long long)bound, ms);
+  }
+}
+
+// the CSR flavours' common part: arrays on the device, except the pairs when h_pairs is given (uploaded batch by batch)
+int mg_import(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows, const uint64_t* d_row_ptr, const uint32_t* d_pairs,
+              const uint32_t* h_pairs, uint64_t max_batch, uint64_t* n_ops, hipStream_t s) {
+  Matrix* m = M(self);
+  MergeScratch& g = mg_of(m);
+  g.flag.need(1);
+  HIP_OK(hipMemsetAsync(g.flag.p, 0, 4, s));
+  hipLaunchKernelGGL(k_mg_csr_check, dim3(std::min<uint32_t>(blocks_for(n_rows), 4096)), dim3(256), 0, s, n_rows, d_row_ptr, g.flag.p);
+  HIP_OK(hipGetLastError());
+  uint64_t nnz = 0;
+  uint32_t bad = 0;
+  HIP_OK(hipMemcpyAsync(&bad, g.flag.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&nnz, d_row_ptr + n_rows, 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (bad) return -1;
+  const uint64_t B = std::min(mg_batch(max_batch), std::max<uint64_t>(nnz, 1));
+  const size_t nb = (size_t)((nnz + B - 1) / B);
+  if (h_pairs && nb) { g.h_pairs[0].need(2 * B); if (nb > 1) g.h_pairs[1].need(2 * B); }
+  cache_sync(m, true);
+  mg_run(self, g, op, s, nb, B,
+         [&](size_t b) { return (uint32_t)std::min<uint64_t>(B, nnz - b * B); },
+         [&](size_t b, uint32_t* rec, hipStream_t e) {
+           const uint64_t t0 = b * B;
+           const uint32_t cnt = (uint32_t)std::min<uint64_t>(B, nnz - t0);
+           const uint32_t* pairs = d_pairs ? d_pairs + 2 * t0 : g.h_pairs[b & 1].p;
+           if (!d_pairs) HIP_OK(hipMemcpyAsync(g.h_pairs[b & 1].p, h_pairs + 2 * t0, (size_t)cnt * 8, hipMemcpyHostToDevice, e));
+           hipLaunchKernelGGL(k_mg_emit_csr, dim3(blocks_for(cnt)), dim3(256), 0, e, n_rows, d_rows, d_row_ptr, pairs, t0, cnt, rec);
+         });
+  if (n_ops) *n_ops = nnz;
+  mg_trim_all(g, false);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops) {
+  if (!mg_op_ok(op) || !dst || !src || dst == src) return -1;
+  Matrix *d = M(dst), *sm = M(src);
+  if (d == sm || d->device != sm->device) return -1;
+  set_device(d);
+  CkptAfter ckpt(dst);                                    // (a checkpoint that falls due is taken after the locks are released)
+  // both matrix locks, lower address first: merge(a, b) and merge(b, a) on two threads cannot wait for each other.  Neither
+  // file lock is needed (nothing here writes a file), so the file-then-matrix order holds trivially.
+  std::unique_lock<std::mutex> l0(d < sm ? d->mu : sm->mu);
+  std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
+  cache_sync(sm, false);
+  cache_sync(d, true);
+  hipStream_t s = d->stream;
+  ExportScratch& x = ex_of(sm);
+  MergeScratch& g = mg_of(d);
+  uint64_t n = 0, nnz = 0;
+  ex_measure(sm, x, SMATRIX_EXPORT_TABLE, s, &n, &nnz);   // the row list, the counts, the first half of their scan
+  if (nnz) {
+    g.ptr.need(n + 1);
+    ex_scan_apply(x, s, x.cnt.p, n, x.cnt_tiles, g.ptr.p);
+    std::vector<uint64_t> ptr(n + 1);
+    HIP_OK(hipMemcpyAsync(ptr.data(), g.ptr.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    // the batches: rows [cut[b], cut[b + 1]), as many whole rows as fit into B ops -- at least one
+    const uint64_t B = mg_batch(max_batch);
+    std::vector<uint32_t> cut{0};
+    uint64_t bound = 0;
+    for (uint64_t r0 = 0; r0 < n;) {
+      uint64_t r1 = std::upper_bound(ptr.begin() + r0 + 1, ptr.end(), ptr[r0] + B) - ptr.begin() - 1;   // the last r1 with ptr[r1] - ptr[r0] <= B
+      if (r1 == r0) r1 = r0 + 1;
+      if (ptr[r1] > ptr[r0]) {                            // (a run of rows without pairs at the end emits nothing)
+        cut.push_back((uint32_t)r1);
+        bound = std::max(bound, ptr[r1] - ptr[r0]);
+      } else if (cut.size() > 1) cut.back() = (uint32_t)r1;
+      else cut[0] = (uint32_t)r1;
+      r0 = r1;
+    }
+    if (bound >= (1ull << 32)) smx_die("merge: a source row of 2^32 pairs");
+    // rows of more than GETROW_WAVE_MAX cells: noted per batch; a cut row's segment counts by arena position (kernels/merge.hpp)
+    // (segments of uncut rows: 128 KiB of cells and up each; of cut rows: 256 KiB each -- two words per entry)
+    g.big.need(2 * ((sm->arena.mapped >> 17) + (sm->arena.mapped >> MG_SEG_SHIFT) + 2) + 1);
+    g.seg_cnt.need((sm->arena.mapped >> MG_SEG_SHIFT) + 2);
+    const uint32_t big_grid = (uint32_t)std::min<uint64_t>(sm->arena.mapped / 8 / GETROW_SEG + 1, 2048);
+    mg_run(dst, g, op, s, cut.size() - 1, bound,
+           [&](size_t b) { return (uint32_t)(ptr[cut[b + 1]] - ptr[cut[b]]); },
+           [&](size_t b, uint32_t* rec, hipStream_t e) {
+             const uint32_t r0 = cut[b], r1 = cut[b + 1];
+             HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
+             hipLaunchKernelGGL(k_mg_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
+                                sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p);
+             hipLaunchKernelGGL(k_mg_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                                r0, rec, g.big.p, g.seg_cnt.p);
+             hipLaunchKernelGGL(k_mg_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                                r0, rec, g.big.p, g.seg_cnt.p);
+           });
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  if (n_ops) *n_ops = nnz;
+  ex_trim_all(x, false);
+  mg_trim_all(g, false);
+  return 0;
+}
+
+int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows, const uint64_t* d_row_ptr,
+                           const uint32_t* d_pairs, uint64_t max_batch, uint64_t* n_ops, void* hip_stream) {
+  if (!mg_op_ok(op) || !self) return -1;
+  if (n_ops) *n_ops = 0;
+  if (n_rows == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  CkptAfter ckpt(self);
+  std::lock_guard<std::mutex> lk(m->mu);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  const int rc = mg_import(self, op, n_rows, d_rows, d_row_ptr, d_pairs, nullptr, max_batch, n_ops, s);
+  if (rc == 0 && !hip_stream) HIP_OK(hipStreamSynchronize(s));
+  return rc;
+}
+
+int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr, const uint32_t* pairs,
+                       uint64_t max_batch, uint64_t* n_ops) {
+  if (!mg_op_ok(op) || !self) return -1;
+  if (n_ops) *n_ops = 0;
+  if (n_rows == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  CkptAfter ckpt(self);
+  std::lock_guard<std::mutex> lk(m->mu);
+  hipStream_t s = m->stream;
+  MergeScratch& g = mg_of(m);
+  g.h_rows.need(n_rows); g.h_ptr.need(n_rows + 1);         // per row; the pairs travel batch by batch (mg_import)
+  HIP_OK(hipMemcpyAsync(g.h_rows.p, rows, n_rows * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(g.h_ptr.p, row_ptr, (n_rows + 1) * 8, hipMemcpyHostToDevice, s));
+  const int rc = mg_import(self, op, n_rows, g.h_rows.p, g.h_ptr.p, nullptr, pairs, max_batch, n_ops, s);
+  HIP_OK(hipStreamSynchronize(s));
+  return rc;
+}
+
+}  // extern "C"

@@ -741,6 +741,7 @@ struct Matrix {
   DevBuf<unsigned long long> cold_keys[3];   // the distinct pending keys, packed; what a round leaves deferred
   void* ex = nullptr;                   // ExportScratch (smx_export.inc): smatrix_export's pooled scratch
   void* rec = nullptr;                  // RecScratch (smx_recommend.inc): smatrix_cf_recommend_batch's pooled scratch
+  void* mg = nullptr;                   // MergeScratch (smx_merge.inc): smatrix_merge / smatrix_import_csr's record buffers, helper stream and events
 };
 
 void set_device(Matrix* m) { HIP_OK(hipSetDevice(m->device)); }
@@ -2001,6 +2002,7 @@ bool file_flush(smatrix_t* self, Matrix* m, bool all, std::unique_lock<std::mute
 void cache_sync(Matrix* m, bool drop);
 void export_release(Matrix* m);
 void recommend_release(Matrix* m);
+void merge_release(Matrix* m);
 
 void apply_dev_locked(smatrix_t* self, int op, size_t n, const uint32_t* x, const uint32_t* y,
                       const uint32_t* v, uint32_t* out, hipStream_t s) {
@@ -2607,6 +2609,7 @@ void smatrix_close(smatrix_t* self) {
       m->row_ret.release();
       export_release(m);
       recommend_release(m);
+      merge_release(m);
       delete static_cast<HostPipe*>(m->host_pipe);
       m->far_tab.release(); m->far_unit_row.release(); m->far_zeros.release(); m->far_occ.release(); m->far_occ0.release(); m->far_clm.release(); m->far_rcnt.release(); m->far_bucket.release(); m->far_prows.release(); m->far_bloom.release(); m->far_unit_info.release(); m->big_list.release(); 
       m->pend_rec.release(); m->pend_keys.release(); m->task_of.release(); m->pend_ctl.release(); m->pend_hash.release();
@@ -3415,6 +3418,9 @@ void smx_stream_release_device(smx_stream_t* st) {
 
 // ---- whole-matrix export (include/smatrix_batch.h) ----------------------------------------------
 #include "smx_export.inc"
+
+// ---- merge of two matrices, CSR import (smatrix_merge / smatrix_import_csr) ------
+#include "smx_merge.inc"
 
 // ---- session recommendations (include/smatrix_batch.h) ------------------------------------------
 #include "smx_recommend.inc"

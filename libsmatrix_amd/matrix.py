@@ -25,6 +25,18 @@ def _export_order(order):
     return _EXPORT_ORDERS[order]
 
 
+_MERGE_OPS = {"set": OP_SET, "incr": OP_INCR, "decr": OP_DECR}
+
+
+def _merge_op(op):
+    """"set" / "incr" / "decr" (or the op code) -> op code; anything else, GET included, is a ValueError"""
+    if op in _MERGE_OPS:
+        return _MERGE_OPS[op]
+    if isinstance(op, int) and not isinstance(op, bool) and op in _MERGE_OPS.values():
+        return op
+    raise ValueError("op must be 'set', 'incr' or 'decr', not %r" % (op,))
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -299,6 +311,93 @@ class SparseMatrix:
         if size[0] * size[1] >= 1 << 63:
             raise ValueError("to_sparse_coo: a %d x %d tensor is beyond torch's element count (rows * columns < 2**63)" % tuple(size))
         return torch.sparse_coo_tensor(torch.stack([x, y]), v, size=tuple(size), is_coalesced=True)
+
+    # ---- merge of two matrices, CSR import (include/smatrix_batch.h smatrix_merge / smatrix_import_csr) ----
+    def merge(self, other, op="incr", max_batch=0):
+        """self[x, y] op= other[x, y] for every pair of other, on the GPU in internal batches of at most
+        max(max_batch, other's longest row) ops (0: 2**24): -> the number of ops applied.  other is not modified."""
+        o = _merge_op(op)
+        if not isinstance(other, SparseMatrix):
+            raise TypeError("merge needs another SparseMatrix, not %r" % (type(other).__name__,))
+        n = C.c_uint64(0)
+        if self._lib.smatrix_merge(self._h, other._h, o, int(max_batch), C.byref(n)) != 0:
+            raise ValueError("smatrix_merge refused: a matrix cannot be merged into itself, and both must be on one device")
+        return n.value
+
+    def __iadd__(self, other):
+        if not isinstance(other, SparseMatrix):
+            return NotImplemented
+        self.merge(other, "incr")
+        return self
+
+    def __isub__(self, other):
+        if not isinstance(other, SparseMatrix):
+            return NotImplemented
+        self.merge(other, "decr")
+        return self
+
+    def import_csr(self, rows, row_ptr, pairs, op="set", max_batch=0):
+        """the inverse of export(): one op per pair of the CSR (rows uint32[n], row_ptr uint64[n+1], pairs uint32[nnz, 2]
+        {column, value}); a row id or a column may repeat (set: the last occurrence wins): -> the number of ops applied"""
+        o = _merge_op(op)
+        rows = _u32(rows)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+        pairs = _u32(pairs)
+        if row_ptr.size != rows.size + 1:
+            raise ValueError("row_ptr must hold len(rows) + 1 entries")
+        if rows.size and 2 * int(row_ptr[-1]) > pairs.size:
+            raise ValueError("pairs holds %d pairs, row_ptr[-1] names %d" % (pairs.size // 2, int(row_ptr[-1])))
+        n = C.c_uint64(0)
+        if self._lib.smatrix_import_csr(self._h, o, rows.size, _p(rows), row_ptr.ctypes.data_as(_lib.u64p), _p(pairs),
+                                        int(max_batch), C.byref(n)) != 0:
+            raise ValueError("smatrix_import_csr refused: row_ptr must start at 0 and never decrease")
+        return n.value
+
+    def import_csr_dev(self, rows, row_ptr, pairs, op="set", max_batch=0, stream=None, n_rows=None):
+        """the same on device arrays: torch tensors as export_dev() returns them (rows int32[n], row_ptr int64[n+1],
+        pairs int32[nnz, 2], contiguous, on the matrix's GPU), or raw device pointers with n_rows given.  stream: a
+        torch.cuda.Stream or a hipStream_t as int (None: the legacy default stream); the import has completed on it when
+        this returns."""
+        o = _merge_op(op)
+        if n_rows is None:
+            for name, t, size in (("rows", rows, 4), ("row_ptr", row_ptr, 8), ("pairs", pairs, 4)):
+                if not t.is_cuda or not t.is_contiguous() or t.element_size() != size or t.is_floating_point():
+                    raise ValueError("%s must be a contiguous %d-byte integer tensor on the GPU" % (name, size))
+            n_rows = rows.numel()
+            if row_ptr.numel() != n_rows + 1:
+                raise ValueError("row_ptr must hold len(rows) + 1 entries")
+            if n_rows and 2 * int(row_ptr[-1].item()) > pairs.numel():
+                raise ValueError("pairs holds %d pairs, row_ptr[-1] names %d" % (pairs.numel() // 2, int(row_ptr[-1].item())))
+            rows, row_ptr, pairs = rows.data_ptr(), row_ptr.data_ptr(), pairs.data_ptr()
+        sp = getattr(stream, "cuda_stream", stream)
+        n = C.c_uint64(0)
+        if self._lib.smatrix_import_csr_dev(self._h, o, int(n_rows), rows, row_ptr, pairs, int(max_batch), C.byref(n), sp) != 0:
+            raise ValueError("smatrix_import_csr_dev refused: row_ptr must start at 0 and never decrease")
+        return n.value
+
+    def from_sparse_coo(self, t, op="incr", max_batch=0):
+        """the inverse of to_sparse_coo(): one op per stored element of a 2-d torch.sparse_coo_tensor of integer values on
+        the matrix's GPU, coalesced or not (an uncoalesced tensor's repeated indices are repeated ops).  Values are taken
+        modulo 2**32; an index beyond uint32 raises ValueError: -> the number of ops applied"""
+        import torch
+        o = _merge_op(op)
+        if t.layout != torch.sparse_coo or t.dim() != 2 or t.dense_dim() != 0:
+            raise ValueError("from_sparse_coo needs a 2-d torch.sparse_coo_tensor")
+        if not t.is_cuda or (self._device is not None and t.device.index != self._device):
+            raise ValueError("from_sparse_coo: the tensor must be on the matrix's GPU")
+        idx, val = t._indices(), t._values()
+        if val.is_floating_point() or val.is_complex() or val.dtype == torch.bool:
+            raise ValueError("from_sparse_coo: integer values only, not %s" % (val.dtype,))
+        if idx.numel() and (int(idx.min().item()) < 0 or int(idx.max().item()) > 0xFFFFFFFF):
+            raise ValueError("from_sparse_coo: an index is beyond uint32")
+        nnz = idx.shape[1]
+        # every element a row of its own: rows = x, row_ptr = 0..nnz, pairs = {y, v}
+        def low32(a):       # the low 32 bits of an int64 tensor as int32 bits
+            return (((a & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000).to(torch.int32)
+        rows = low32(idx[0]).contiguous()
+        row_ptr = torch.arange(nnz + 1, dtype=torch.int64, device=idx.device)
+        pairs = torch.stack([low32(idx[1]), low32(val.to(torch.int64))], dim=1).contiguous()
+        return self.import_csr_dev(rows, row_ptr, pairs, o, max_batch)
 
     # ---- introspection --------------------------------------------------------
     def stats(self):

@@ -18,7 +18,7 @@ with tempfile.NamedTemporaryFile(suffix=".co") as f:
 cur = {}
 rows = []
 for line in notes.splitlines():
-    m = re.match(r"\s+\.(name|sgpr_count|vgpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size):\s+(\S+)", line)
+    m = re.match(r"\s+\.(name|sgpr_count|vgpr_count|sgpr_spill_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\S+)", line)
     if not m: continue
     if m.group(1) in cur: rows.append(cur); cur = {}
     cur[m.group(1)] = m.group(2)
@@ -26,4 +26,4 @@ if cur: rows.append(cur)
 for r in rows:
     name = subprocess.run(["c++filt", r.get("name", "?")], capture_output=True, text=True).stdout.strip().split("(")[0]
     if flt in name:
-        print("%-48s sgpr %3s (spilled %2s)  vgpr %3s (spilled %s)  lds %s" % (name[-48:], r.get("sgpr_count"), r.get("sgpr_spill_count"), r.get("vgpr_count"), r.get("vgpr_spill_count"), r.get("group_segment_fixed_size")))
+        print("%-48s sgpr %3s (spilled %2s)  vgpr %3s (spilled %s)  lds %s  scratch %s" % (name[-48:], r.get("sgpr_count"), r.get("sgpr_spill_count"), r.get("vgpr_count"), r.get("vgpr_spill_count"), r.get("group_segment_fixed_size"), r.get("private_segment_fixed_size")))
