@@ -188,6 +188,37 @@ int smatrix_export_dev(smatrix_t* self, int order, uint64_t cap_rows, uint64_t c
  *   on the matrix's GPU, work ordered after hip_stream's earlier work and complete on it when the call returns (NULL = the
  *   legacy default stream). */
 int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops);
+
+/* smatrix_merge_scaled: smatrix_merge with a decay and a filter between src's row tables and the ops -- the call that ends a
+ *   sliding-window cycle (total += today; total -= day_30; fresh = merge_scaled(empty, total, SET, 1, 1, 1): no dead cells, row
+ *   tables of the size the survivors need) and the exponential forgetting of a CF recommender (num / den < 1).
+ * Candidates: every pair (y, v) that smatrix_export(src, TABLE) lists under row x -- the pairs smatrix_merge applies.
+ * Transform:  v' = floor(v * num / den), computed in 64 bits; 1 <= num <= den, so v' <= v and nothing overflows.
+ * Filter:     a candidate is DROPPED when v' < min_value, or when y == 0 && v' == 0 (a (0, 0) cell is the empty slot, quirk Q3:
+ *             it cannot be stored, and applying it would only cut probe chains).
+ * Every other candidate is applied once as op(x, y, v'); op is SMATRIX_OP_SET, _INCR or _DECR.
+ * *n_ops (may be NULL) receives the number of ops applied, *n_dropped (may be NULL) the number of candidates dropped; their
+ *   sum is src's pair count.
+ * So: num == den and min_value == 0 behaves as smatrix_merge (but for a (0, 0) pair, which the export never lists anyway).
+ *   min_value == 1 drops every dead cell.  With min_value == 0 a (y != 0, 0) result still creates its cell (an incr by 0 does
+ *   so in the reference).  A source row that loses all its pairs contributes nothing and is not created in dst.
+ * Result: the batch contract at the top of this file for the whole call as if it were ONE batch: the final state is what the
+ *   reference reaches by applying those ops one by one in some order; values are exact (uint32, wrapping); row sizes and `used`
+ *   are the reference's -- into an empty dst, those of a matrix that never held the dropped pairs.  SET ties cannot occur:
+ *   every key occurs once.  Nothing beyond the batch contract is promised for the layout of a row's table.
+ * Bounded scratch: the work runs in internal batches of at most max(max_batch, longest SURVIVING row) ops -- max_batch == 0:
+ *   2^24; above 2^31: 2^31.  Device memory taken beyond the matrices is proportional to that bound plus 20 bytes per source ROW
+ *   (row list 8, survivor count 4, scan 8), never to the number of pairs.  The result does not depend on max_batch in anything
+ *   the contract fixes (values, row set, sizes, `used`).
+ * Returns 0; -1 and nothing changed for: an op other than SET / INCR / DECR, dst == src, the two matrices on different devices,
+ *   den == 0, num == 0, num > den.
+ * Locks and mirrors: both matrices' locks are held for the call, taken in address order; no file lock is taken.  Scalar writes
+ *   still in src's and dst's host mirrors are written back first and dst's mirror is dropped.  File-backed dst and src work
+ *   unchanged; smatrix_stats_t::batches counts the internal batches, and a call during which SMATRIX_FLUSH_EVERY falls due
+ *   takes ONE checkpoint, at its end.  src is not modified (its tables never shrink in place: build the pruned matrix, then
+ *   close the old one).  Runs on dst's own stream and returns when done. */
+int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, uint32_t den, uint32_t min_value,
+                         uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped);
 int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr,
                        const uint32_t* pairs, uint64_t max_batch, uint64_t* n_ops);
 int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows,

@@ -14,6 +14,17 @@
 //                      before it
 // Each source cell is read once (twice in a row of >= 2 segments) and 12 bytes leave per pair.
 //
+// smatrix_merge_scaled runs the same row walkers with a TRANSFORM between the cell and the record: the bodies below are
+// templated on a functor  bool f(key, value&)  that rewrites the value of a non-empty cell and says whether the pair survives.
+// MgIdent (smatrix_merge: every pair as it is) folds away; MgScale is v' = floor(v * num / den) with the two drop rules.
+//   k_mgx_count        the SURVIVORS of every row of the row list -> cnt[] (what k_ex_count is to the export), a wave per row up to
+//                      GETROW_WAVE_MAX cells; longer rows get cnt 0 and one {row, segment} entry per segment in `big`
+//   k_mgx_count_big    those segments, a 1024-lane workgroup each: adds the segment's survivors to cnt[row] and, in a cut row,
+//                      leaves them in seg_cnt[] -- for the whole matrix at once, so the emission has no counting pass of its own
+//   k_mgx_emit, k_mgx_emit_big   k_mg_emit / k_mg_emit_big<false> with the transform
+// Both count kernels also sum the non-empty cells they saw into *tot: dropped = *tot - survivors.  A source cell is read twice
+// in all: once counted, once emitted.
+//
 // A cut row's segment counts live in seg_cnt[] at (byte offset of the segment in the arena) >> 18: a segment is 256 KiB of
 // cells and rows do not overlap, so no two segments of any two rows share an index, and the array is arena / 65536 bytes -- no
 // plan pass that numbers the segments.
@@ -26,14 +37,43 @@ __device__ __forceinline__ void mg_put(uint32_t* __restrict__ rec, uint64_t at, 
   p[0] = x; p[1] = key; p[2] = val;
 }
 
-__global__ __launch_bounds__(256) void k_mg_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
-                                                 const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
-                                                 uint32_t* __restrict__ rec, uint32_t* big) {
+struct MgIdent {
+  __device__ __forceinline__ bool operator()(uint32_t, uint32_t&) const { return true; }
+};
+
+// floor(v * num / den) for 1 <= num <= den, exactly, without a 64-bit division.  n = v * num < 2^64 and the quotient is <= v.
+// The estimate: n as a double (hi * 2^32 + lo: both parts exact, the fma rounds once), times the rounded 1 / den, rounded again
+// -- three roundings of 2^-53 relative each on a quotient below 2^32, so it is off by less than 2^-19 from n / den and its
+// integer part is the quotient, or one beside it.  The remainder (64-bit, wrapping; it lies in [-den, 2 * den)) says which.
+__host__ __device__ __forceinline__ uint32_t mg_scale_value(uint32_t v, uint32_t num, uint32_t den, double rden) {
+  const uint64_t n = (uint64_t)v * num;
+  const double d = fma((double)(uint32_t)(n >> 32), 4294967296.0, (double)(uint32_t)n);
+  uint32_t q = (uint32_t)fmin(d * rden, 4294967295.0);
+  const int64_t r = (int64_t)(n - (uint64_t)q * den);
+  if (r < 0) q--;
+  else if (r >= (int64_t)den) q++;
+  return q;
+}
+
+// smatrix_merge_scaled's transform and filter: the pair survives unless v' < min_value or it would be the empty slot (0, 0)
+struct MgScale {
+  uint32_t num, den, min_value;
+  double rden;                                             // 1.0 / den
+  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
+    if (num != den) val = mg_scale_value(val, num, den, rden);
+    return val >= min_value && (key | val) != 0;
+  }
+};
+
+template <typename F>
+__device__ __forceinline__ void mg_emit_rows(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                             const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                             uint32_t* __restrict__ rec, uint32_t* big, const uint32_t wave, const uint32_t nwaves,
+                                             const F f) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
   const uint64_t lt = (1ull << lane) - 1;
   const uint64_t base = ptr[r0];
-  for (uint32_t r = r0 + ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); r < r1; r += nwaves) {
+  for (uint32_t r = r0 + wave; r < r1; r += nwaves) {
     const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
     if (s.z == 0) continue;                                            // no block yet (quirk Q3): no pairs
     const uint32_t size = 1u << meta_lg(s.x);
@@ -53,12 +93,13 @@ __global__ __launch_bounds__(256) void k_mg_emit(const DirSlot* __restrict__ dir
       return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
     };
     auto step = [&](const uint4 c) {                                   // compacts the 128 cells held in c (slot order)
-      const bool ne0 = (c.x | c.y) != 0, ne1 = (c.z | c.w) != 0;
+      uint32_t v0 = c.y, v1 = c.w;
+      const bool ne0 = (c.x | c.y) != 0 && f(c.x, v0), ne1 = (c.z | c.w) != 0 && f(c.z, v1);
       const uint64_t m0 = __ballot(ne0), m1 = __ballot(ne1);
       uint64_t o = at + (uint32_t)__popcll(m0 & lt) + (uint32_t)__popcll(m1 & lt);
-      if (ne0) mg_put(rec, o, x, c.x, c.y);
+      if (ne0) mg_put(rec, o, x, c.x, v0);
       o += ne0;
-      if (ne1) mg_put(rec, o, x, c.z, c.w);
+      if (ne1) mg_put(rec, o, x, c.z, v1);
       at += (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
     };
     // every load of a row of up to 512 cells (the CF shape and four times that) is in flight before the first is consumed
@@ -73,10 +114,23 @@ __global__ __launch_bounds__(256) void k_mg_emit(const DirSlot* __restrict__ dir
   }
 }
 
-template <bool COUNT>
-__global__ __launch_bounds__(1024) void k_mg_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
-                                                      const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
-                                                      const uint32_t* big, uint32_t* seg_cnt) {
+__global__ __launch_bounds__(256) void k_mg_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                 const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                 uint32_t* __restrict__ rec, uint32_t* big) {
+  // (the wave's number and the number of waves are taken here: blockDim is a constant of the launch to a kernel only)
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, MgIdent());
+}
+
+__global__ __launch_bounds__(256) void k_mgx_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgScale f) {
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, f);
+}
+
+template <bool COUNT, typename F>
+__device__ __forceinline__ void mg_emit_segs(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                             const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                             const uint32_t* big, uint32_t* seg_cnt, const F f) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t s_written;
   const uint32_t nent = big[0];
@@ -108,7 +162,8 @@ __global__ __launch_bounds__(1024) void k_mg_emit_big(const DirSlot* __restrict_
         uint32_t c = 0;
         for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
           const uint4 q = cells[(p0 >> 1) + threadIdx.x];
-          c += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+          uint32_t v0 = q.y, v1 = q.w;
+          c += ((q.x | q.y) != 0 && f(q.x, v0)) + ((q.z | q.w) != 0 && f(q.z, v1));
         }
         c = block_sum(c);
         if (threadIdx.x == 0) seg_cnt[first + g] = c;
@@ -126,21 +181,105 @@ __global__ __launch_bounds__(1024) void k_mg_emit_big(const DirSlot* __restrict_
       for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
         const uint32_t written = s_written;
         const uint4 c = cells[(p0 >> 1) + threadIdx.x];
-        const bool ne0 = (c.x | c.y) != 0, ne1 = (c.z | c.w) != 0;
+        uint32_t v0 = c.y, v1 = c.w;
+        const bool ne0 = (c.x | c.y) != 0 && f(c.x, v0), ne1 = (c.z | c.w) != 0 && f(c.z, v1);
         const uint64_t m0 = __ballot(ne0), m1 = __ballot(ne1);
         if (lane == 0) wsum[w] = (uint32_t)__popcll(m0) + (uint32_t)__popcll(m1);
         __syncthreads();
         uint32_t before = 0, total = 0;
         for (uint32_t i = 0; i < 16; i++) { const uint32_t v = wsum[i]; if (i < w) before += v; total += v; }
         uint64_t o = off + written + before + (uint32_t)__popcll(m0 & lt) + (uint32_t)__popcll(m1 & lt);
-        if (ne0) mg_put(rec, o, s.y, c.x, c.y);
+        if (ne0) mg_put(rec, o, s.y, c.x, v0);
         o += ne0;
-        if (ne1) mg_put(rec, o, s.y, c.z, c.w);
+        if (ne1) mg_put(rec, o, s.y, c.z, v1);
         __syncthreads();
         if (threadIdx.x == 0) s_written = written + total;
         __syncthreads();
       }
     }
+  }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mg_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                      const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                      const uint32_t* big, uint32_t* seg_cnt) {
+  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, MgIdent());
+}
+
+// (the cut rows' seg_cnt entries are k_mgx_count_big's, of this very transform)
+__global__ __launch_bounds__(1024) void k_mgx_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                       const uint32_t* big, uint32_t* seg_cnt, const MgScale f) {
+  mg_emit_segs<false>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
+}
+
+// ---- the filtered counts of smatrix_merge_scaled ----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_mgx_count(const DirSlot* __restrict__ dir, uint8_t* arena, uint32_t n,
+                                                   const uint64_t* __restrict__ items, uint32_t* __restrict__ cnt, uint32_t* big,
+                                                   unsigned long long* tot, const MgScale f) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  uint32_t seen = 0;                                                   // this lane's non-empty cells, over all the wave's rows
+  for (uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n; r += nwaves) {
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
+    if (size > GETROW_WAVE_MAX) {                                      // as k_mg_emit: one entry {row, segment} per segment
+      const uint32_t nseg = getrow_nseg(size);
+      uint32_t e0 = 0;
+      if (lane == 0) { cnt[r] = 0; e0 = atomicAdd(&big[0], nseg); }
+      e0 = (uint32_t)__shfl((int)e0, 0);
+      for (uint32_t g = lane; g < nseg; g += 64) { big[1 + 2 * (e0 + g)] = r; big[2 + 2 * (e0 + g)] = g; }
+      continue;
+    }
+    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
+    uint32_t c = 0;
+    for (uint32_t p = 2 * lane; p < size; p += 128) {
+      uint4 q = cells[p >> 1];
+      const bool ne0 = (q.x | q.y) != 0, ne1 = (q.z | q.w) != 0;
+      seen += ne0 + ne1;
+      c += (ne0 && f(q.x, q.y)) + (ne1 && f(q.z, q.w));
+    }
+    for (uint32_t d = 32; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
+    if (lane == 0) cnt[r] = c;
+  }
+  for (uint32_t d = 32; d; d >>= 1) seen += (uint32_t)__shfl_xor((int)seen, d);   // (a wave's rows hold < 2^32 cells: rows * 8192 / waves)
+  if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+}
+
+__global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                        uint32_t* cnt, const uint32_t* big, uint32_t* seg_cnt, unsigned long long* tot,
+                                                        const MgScale f) {
+  __shared__ uint32_t wsum[2][16];
+  const uint32_t nent = big[0];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint32_t t = blockIdx.x; t < nent; t += gridDim.x) {
+    const uint32_t r = big[1 + 2 * t], g = big[2 + 2 * t];
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = 1u << meta_lg(s.x);                          // > GETROW_WAVE_MAX: a multiple of 2048
+    const uint32_t nseg = getrow_nseg(size);
+    const uint8_t* cell_bytes = reinterpret_cast<const uint8_t*>(row_cells(arena, s.z));
+    const uint4* cells = reinterpret_cast<const uint4*>(cell_bytes);
+    const uint32_t p_begin = nseg == 1 ? 0u : g * GETROW_SEG, p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
+    uint32_t c = 0, seen = 0;
+    for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
+      uint4 q = cells[(p0 >> 1) + threadIdx.x];
+      const bool ne0 = (q.x | q.y) != 0, ne1 = (q.z | q.w) != 0;
+      seen += ne0 + ne1;
+      c += (ne0 && f(q.x, q.y)) + (ne1 && f(q.z, q.w));
+    }
+    for (uint32_t d = 32; d; d >>= 1) { c += (uint32_t)__shfl_xor((int)c, d); seen += (uint32_t)__shfl_xor((int)seen, d); }
+    if (lane == 0) { wsum[0][w] = c; wsum[1][w] = seen; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t tc = 0, ts = 0;
+      for (uint32_t i = 0; i < 16; i++) { tc += wsum[0][i]; ts += wsum[1][i]; }
+      // (an uncut row's table may share its 256 KiB with another row's: only cut rows own their seg_cnt entries)
+      if (nseg > 1) seg_cnt[((uint64_t)(cell_bytes - arena) >> MG_SEG_SHIFT) + g] = tc;
+      if (tc) atomicAdd(&cnt[r], tc);
+      if (ts) atomicAdd(tot, (unsigned long long)ts);
+    }
+    __syncthreads();
   }
 }
 

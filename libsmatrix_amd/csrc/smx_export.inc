@@ -104,8 +104,8 @@ void ex_radix(ExportScratch& x, hipStream_t s, uint64_t* data, const std::vector
   HIP_OK(hipStreamSynchronize(s));                                // (the host arrays above are the sources of the copies)
 }
 
-// steps 1 and 2: the row list and the counts in scratch; *n_out / *nnz_out = rows / pairs
-void ex_measure(Matrix* m, ExportScratch& x, int order, hipStream_t s, uint64_t* n_out, uint64_t* nnz_out) {
+// step 1: the row list in x.items; returns the number of rows
+uint64_t ex_row_list(Matrix* m, ExportScratch& x, int order, hipStream_t s) {
   const uint32_t dsz = m->dir_size;
   const uint32_t ntd = (dsz + EX_TILE - 1) / EX_TILE;
   x.tcnt.need(ntd); x.toff.need((size_t)ntd + 1);
@@ -115,12 +115,20 @@ void ex_measure(Matrix* m, ExportScratch& x, int order, hipStream_t s, uint64_t*
   ex_scan_apply(x, s, x.tcnt.p, ntd, nt, x.toff.p);
   const uint64_t n = ex_read(x.toff.p + ntd, s);
   x.cnt_tiles = 0;
-  uint64_t nnz = 0;
   if (n) {
     x.items.need(n);
     hipLaunchKernelGGL(k_ex_dir_write, dim3(ntd), dim3(EX_THREADS), 0, s, m->d_dir, dsz, x.toff.p, x.items.p);
     HIP_OK(hipGetLastError());
     if (order == SMATRIX_EXPORT_SORTED && n > 1) ex_radix(x, s, x.items.p, {0}, {n});
+  }
+  return n;
+}
+
+// steps 1 and 2: the row list and the counts in scratch; *n_out / *nnz_out = rows / pairs
+void ex_measure(Matrix* m, ExportScratch& x, int order, hipStream_t s, uint64_t* n_out, uint64_t* nnz_out) {
+  const uint64_t n = ex_row_list(m, x, order, s);
+  uint64_t nnz = 0;
+  if (n) {
     x.cnt.need(n); x.l0.need(n + 1);                              // l0: the rows of more than GETROW_WAVE_MAX cells
     HIP_OK(hipMemsetAsync(x.l0.p, 0, 4, s));
     hipLaunchKernelGGL(k_ex_count, dim3(std::min<uint32_t>(blocks_for(n * 64), 16384)), dim3(EX_THREADS), 0, s, m->d_dir,

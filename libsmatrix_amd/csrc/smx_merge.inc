@@ -1,4 +1,5 @@
-// smx_merge.inc -- smatrix_merge / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h), host side.
+// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h),
+// host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_measure and scan);
 // the device code is kernels/merge.hpp.
 //
@@ -12,6 +13,8 @@
 // CSR:   the batches are runs of max_batch pairs, wherever the rows' borders fall
 // Device memory: two record buffers of 12 * bound bytes, the write path's own scratch for a batch of `bound` ops, and per ROW of
 // the source 8 (row list) + 4 (counts) + 8 (scan) bytes -- nothing per pair.
+// merge_scaled: merge with the counts of the SURVIVORS of its transform (k_mgx_count*, instead of the export's k_ex_count*) under
+//        the same scan, so the cuts and the rows' record offsets are those of what k_mgx_emit* will write; same memory.
 
 namespace {
 
@@ -21,6 +24,7 @@ constexpr uint64_t MG_MAX_BATCH = 1ull << 31;          // (a write batch holds f
 struct MergeScratch {
   DevBuf<uint32_t> rec[2], big, seg_cnt, flag, h_rows, h_pairs[2];
   DevBuf<uint64_t> ptr, h_ptr;
+  DevBuf<unsigned long long> tot;                        // merge_scaled: the candidates the count kernels saw
   hipStream_t e = nullptr;                               // the helper stream: emission
   hipEvent_t ev_start = nullptr, ev_rec[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
 };
@@ -42,6 +46,7 @@ MergeScratch& mg_of(Matrix* m) {
 void mg_trim_all(MergeScratch& g, bool all) {
   ex_trim(g.rec[0], all); ex_trim(g.rec[1], all); ex_trim(g.big, all); ex_trim(g.seg_cnt, all); ex_trim(g.flag, all);
   ex_trim(g.h_rows, all); ex_trim(g.h_pairs[0], all); ex_trim(g.h_pairs[1], all); ex_trim(g.ptr, all); ex_trim(g.h_ptr, all);
+  ex_trim(g.tot, all);
 }
 
 void merge_release(Matrix* m) {
@@ -138,6 +143,44 @@ int mg_import(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows, 
   return 0;
 }
 
+// merge / merge_scaled once the counts of the source's n rows are in x.cnt and the first half of their scan is done
+// (x.cnt_tiles): the second half, the batches cut on the host, the loop.  emit(r0, r1, rec, e) enqueues the kernels that write
+// the records of the rows [r0, r1) of the row list on stream e.  The caller holds both locks.
+template <typename EmitRows>
+void mg_run_rows(smatrix_t* dst, ExportScratch& x, MergeScratch& g, int op, hipStream_t s, uint64_t n, uint64_t max_batch, EmitRows emit) {
+  g.ptr.need(n + 1);
+  ex_scan_apply(x, s, x.cnt.p, n, x.cnt_tiles, g.ptr.p);
+  std::vector<uint64_t> ptr(n + 1);
+  HIP_OK(hipMemcpyAsync(ptr.data(), g.ptr.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  // the batches: rows [cut[b], cut[b + 1]), as many whole rows as fit into B ops -- at least one
+  const uint64_t B = mg_batch(max_batch);
+  std::vector<uint32_t> cut{0};
+  uint64_t bound = 0;
+  for (uint64_t r0 = 0; r0 < n;) {
+    uint64_t r1 = std::upper_bound(ptr.begin() + r0 + 1, ptr.end(), ptr[r0] + B) - ptr.begin() - 1;   // the last r1 with ptr[r1] - ptr[r0] <= B
+    if (r1 == r0) r1 = r0 + 1;
+    if (ptr[r1] > ptr[r0]) {                              // (a run of rows without pairs at the end emits nothing)
+      cut.push_back((uint32_t)r1);
+      bound = std::max(bound, ptr[r1] - ptr[r0]);
+    } else if (cut.size() > 1) cut.back() = (uint32_t)r1;
+    else cut[0] = (uint32_t)r1;
+    r0 = r1;
+  }
+  if (bound >= (1ull << 32)) smx_die("merge: a source row of 2^32 pairs");
+  mg_run(dst, g, op, s, cut.size() - 1, bound,
+         [&](size_t b) { return (uint32_t)(ptr[cut[b + 1]] - ptr[cut[b]]); },
+         [&](size_t b, uint32_t* rec, hipStream_t e) { emit(cut[b], cut[b + 1], rec, e); });
+}
+
+// rows of more than GETROW_WAVE_MAX cells: noted per batch; a cut row's segment counts by arena position (kernels/merge.hpp)
+// (segments of uncut rows: 128 KiB of cells and up each; of cut rows: 256 KiB each -- two words per entry)
+void mg_need_big(MergeScratch& g, Matrix* sm) {
+  g.big.need(2 * ((sm->arena.mapped >> 17) + (sm->arena.mapped >> MG_SEG_SHIFT) + 2) + 1);
+  g.seg_cnt.need((sm->arena.mapped >> MG_SEG_SHIFT) + 2);
+}
+uint32_t mg_big_grid(Matrix* sm) { return (uint32_t)std::min<uint64_t>(sm->arena.mapped / 8 / GETROW_SEG + 1, 2048); }
+
 }  // namespace
 
 extern "C" {
@@ -160,46 +203,81 @@ int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, ui
   uint64_t n = 0, nnz = 0;
   ex_measure(sm, x, SMATRIX_EXPORT_TABLE, s, &n, &nnz);   // the row list, the counts, the first half of their scan
   if (nnz) {
-    g.ptr.need(n + 1);
-    ex_scan_apply(x, s, x.cnt.p, n, x.cnt_tiles, g.ptr.p);
-    std::vector<uint64_t> ptr(n + 1);
-    HIP_OK(hipMemcpyAsync(ptr.data(), g.ptr.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    // the batches: rows [cut[b], cut[b + 1]), as many whole rows as fit into B ops -- at least one
-    const uint64_t B = mg_batch(max_batch);
-    std::vector<uint32_t> cut{0};
-    uint64_t bound = 0;
-    for (uint64_t r0 = 0; r0 < n;) {
-      uint64_t r1 = std::upper_bound(ptr.begin() + r0 + 1, ptr.end(), ptr[r0] + B) - ptr.begin() - 1;   // the last r1 with ptr[r1] - ptr[r0] <= B
-      if (r1 == r0) r1 = r0 + 1;
-      if (ptr[r1] > ptr[r0]) {                            // (a run of rows without pairs at the end emits nothing)
-        cut.push_back((uint32_t)r1);
-        bound = std::max(bound, ptr[r1] - ptr[r0]);
-      } else if (cut.size() > 1) cut.back() = (uint32_t)r1;
-      else cut[0] = (uint32_t)r1;
-      r0 = r1;
-    }
-    if (bound >= (1ull << 32)) smx_die("merge: a source row of 2^32 pairs");
-    // rows of more than GETROW_WAVE_MAX cells: noted per batch; a cut row's segment counts by arena position (kernels/merge.hpp)
-    // (segments of uncut rows: 128 KiB of cells and up each; of cut rows: 256 KiB each -- two words per entry)
-    g.big.need(2 * ((sm->arena.mapped >> 17) + (sm->arena.mapped >> MG_SEG_SHIFT) + 2) + 1);
-    g.seg_cnt.need((sm->arena.mapped >> MG_SEG_SHIFT) + 2);
-    const uint32_t big_grid = (uint32_t)std::min<uint64_t>(sm->arena.mapped / 8 / GETROW_SEG + 1, 2048);
-    mg_run(dst, g, op, s, cut.size() - 1, bound,
-           [&](size_t b) { return (uint32_t)(ptr[cut[b + 1]] - ptr[cut[b]]); },
-           [&](size_t b, uint32_t* rec, hipStream_t e) {
-             const uint32_t r0 = cut[b], r1 = cut[b + 1];
-             HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
-             hipLaunchKernelGGL(k_mg_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
-                                sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p);
-             hipLaunchKernelGGL(k_mg_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                                r0, rec, g.big.p, g.seg_cnt.p);
-             hipLaunchKernelGGL(k_mg_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                                r0, rec, g.big.p, g.seg_cnt.p);
-           });
+    mg_need_big(g, sm);
+    const uint32_t big_grid = mg_big_grid(sm);
+    mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
+      hipLaunchKernelGGL(k_mg_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
+                         sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p);
+      hipLaunchKernelGGL(k_mg_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                         r0, rec, g.big.p, g.seg_cnt.p);
+      hipLaunchKernelGGL(k_mg_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                         r0, rec, g.big.p, g.seg_cnt.p);
+    });
   }
   HIP_OK(hipStreamSynchronize(s));
   if (n_ops) *n_ops = nnz;
+  ex_trim_all(x, false);
+  mg_trim_all(g, false);
+  return 0;
+}
+
+int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, uint32_t den, uint32_t min_value, uint64_t max_batch,
+                         uint64_t* n_ops, uint64_t* n_dropped) {
+  if (!mg_op_ok(op) || !dst || !src || dst == src || num == 0 || num > den) return -1;    // (num >= 1, so den == 0 is num > den)
+  Matrix *d = M(dst), *sm = M(src);
+  if (d == sm || d->device != sm->device) return -1;
+  set_device(d);
+  CkptAfter ckpt(dst);
+  std::unique_lock<std::mutex> l0(d < sm ? d->mu : sm->mu);   // (locks, mirrors, stream: as smatrix_merge)
+  std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
+  cache_sync(sm, false);
+  cache_sync(d, true);
+  hipStream_t s = d->stream;
+  ExportScratch& x = ex_of(sm);
+  MergeScratch& g = mg_of(d);
+  const MgScale f{num, den, min_value, 1.0 / (double)den};
+  const uint64_t n = ex_row_list(sm, x, SMATRIX_EXPORT_TABLE, s);
+  uint64_t kept = 0;
+  unsigned long long seen = 0;
+  if (n) {
+    // the survivors of every row (and of every segment of a cut row) and the candidates in all: the one counting pass
+    x.cnt.need(n);
+    mg_need_big(g, sm);
+    g.tot.need(1);
+    const uint32_t big_grid = mg_big_grid(sm);
+    HIP_OK(hipMemsetAsync(g.big.p, 0, 4, s));
+    HIP_OK(hipMemsetAsync(g.tot.p, 0, 8, s));
+    hipEvent_t tev[2] = {nullptr, nullptr};
+    if (d->profile) { for (hipEvent_t& ev : tev) HIP_OK(hipEventCreate(&ev)); HIP_OK(hipEventRecord(tev[0], s)); }
+    hipLaunchKernelGGL(k_mgx_count, dim3(std::min<uint32_t>(blocks_for(n * 64), 16384)), dim3(256), 0, s, sm->d_dir, sm->arena.base,
+                       (uint32_t)n, x.items.p, x.cnt.p, g.big.p, g.tot.p, f);
+    hipLaunchKernelGGL(k_mgx_count_big, dim3(big_grid), dim3(1024), 0, s, sm->d_dir, sm->arena.base, x.items.p, x.cnt.p, g.big.p,
+                       g.seg_cnt.p, g.tot.p, f);
+    HIP_OK(hipGetLastError());
+    if (d->profile) HIP_OK(hipEventRecord(tev[1], s));
+    x.cnt_tiles = ex_scan_prep(x, s, x.cnt.p, n);
+    HIP_OK(hipMemcpyAsync(&seen, g.tot.p, 8, hipMemcpyDeviceToHost, s));
+    kept = ex_read(x.part.p + x.cnt_tiles, s);
+    if (d->profile) {
+      float ms = 0;
+      HIP_OK(hipEventElapsedTime(&ms, tev[0], tev[1]));
+      for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
+      fprintf(stderr, "[smatrix] merge_scaled: filtered count %.3f ms, %llu of %llu pairs survive\n", ms, (unsigned long long)kept, seen);
+    }
+    if (kept) {
+      mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+        HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
+        hipLaunchKernelGGL(k_mgx_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
+                           sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p, f);
+        hipLaunchKernelGGL(k_mgx_emit_big, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                           r0, rec, g.big.p, g.seg_cnt.p, f);
+      });
+    }
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  if (n_ops) *n_ops = kept;
+  if (n_dropped) *n_dropped = seen - kept;
   ex_trim_all(x, false);
   mg_trim_all(g, false);
   return 0;

@@ -37,6 +37,15 @@ def _merge_op(op):
     raise ValueError("op must be 'set', 'incr' or 'decr', not %r" % (op,))
 
 
+def _scale_args(num, den, min_value):
+    """merge_scaled's num / den / min_value: uint32 each, 1 <= num <= den; anything else is a ValueError"""
+    for name, val in (("num", num), ("den", den), ("min_value", min_value)):
+        if not isinstance(val, (int, np.integer)) or isinstance(val, bool) or not 0 <= val <= 0xFFFFFFFF:
+            raise ValueError("%s must be an integer in 0 .. 2**32 - 1, not %r" % (name, val))
+    if not 1 <= num <= den:
+        raise ValueError("1 <= num <= den is required, not %r / %r" % (num, den))
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -323,6 +332,33 @@ class SparseMatrix:
         if self._lib.smatrix_merge(self._h, other._h, o, int(max_batch), C.byref(n)) != 0:
             raise ValueError("smatrix_merge refused: a matrix cannot be merged into itself, and both must be on one device")
         return n.value
+
+    def merge_scaled(self, other, op="incr", num=1, den=1, min_value=0, max_batch=0):
+        """merge with a decay and a filter: every pair (y, v) of other becomes v' = v * num // den and is dropped when
+        v' < min_value (or when it would be the empty cell (0, 0)); the others are applied as self[x, y] op= v'.
+        1 <= num <= den <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified."""
+        o = _merge_op(op)
+        _scale_args(num, den, min_value)
+        if not isinstance(other, SparseMatrix):
+            raise TypeError("merge_scaled needs another SparseMatrix, not %r" % (type(other).__name__,))
+        n, dropped = C.c_uint64(0), C.c_uint64(0)
+        if self._lib.smatrix_merge_scaled(self._h, other._h, o, int(num), int(den), int(min_value), int(max_batch),
+                                          C.byref(n), C.byref(dropped)) != 0:
+            raise ValueError("smatrix_merge_scaled refused: a matrix cannot be merged into itself, and both must be on one device")
+        return n.value, dropped.value
+
+    def pruned(self, min_value=1, num=1, den=1, filename=None):
+        """a NEW matrix (in memory, or file-backed when filename is given) that holds self's pairs scaled by num / den, without
+        those below min_value: no dead cells, row tables as small as the survivors allow -- the end of a sliding-window cycle
+        (total += today; total -= day_30; total = total.pruned()).  self is not modified."""
+        _scale_args(num, den, min_value)
+        m = SparseMatrix(filename)
+        try:
+            m.merge_scaled(self, "set", num, den, min_value)
+        except Exception:
+            m.close()
+            raise
+        return m
 
     def __iadd__(self, other):
         if not isinstance(other, SparseMatrix):
