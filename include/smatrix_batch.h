@@ -219,6 +219,39 @@ int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, ui
  *   close the old one).  Runs on dst's own stream and returns when done. */
 int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, uint32_t den, uint32_t min_value,
                          uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped);
+
+/* smatrix_merge_topk: smatrix_merge that keeps, of every row of src, only the m heaviest pairs -- the neighbourhood truncation of
+ *   an item-kNN recommender (total += today; total -= day_30; serving = merge_topk(empty, total, SET, m, 1): every row of the
+ *   serving copy holds at most m + 1 pairs, whatever the row held in total).
+ * Candidates: every pair (y, v) that smatrix_export(src, TABLE) lists under row x -- the pairs smatrix_merge applies.
+ * Head pair:  the pair with y == 0 (the CF example's per-item total) is kept iff v >= min_value && v != 0 (a (0, 0) cell is the
+ *             empty slot, quirk Q3) and never counts against m: the kept pairs score in the copy as they do in src, and the
+ *             cosine needs the totals of both items.
+ * Eligible:   y != 0 && v >= min_value.  With min_value == 0 a dead cell (y != 0, v == 0) is eligible, ranks below every live
+ *             pair and, when kept, creates its cell in dst as in smatrix_merge.
+ * Rank:       key(y, v) = ((uint64_t)v << 32) | (0xFFFFFFFF - y), larger is better: by value, equal values by ascending column.
+ *             Keys are unique within a row; the row keeps its min(m, eligible) eligible pairs of the largest keys.  The kept set
+ *             depends on src's contents alone -- not on slot order, insertion history or max_batch.
+ * Every kept pair is applied once as op(x, y, v); op is SMATRIX_OP_SET, _INCR or _DECR.  Everything else is dropped.
+ * *n_ops (may be NULL) receives the number of ops applied, *n_dropped (may be NULL) the number of candidates dropped; their
+ *   sum is src's pair count.  A source row that keeps nothing contributes nothing and is not created in dst.
+ * Result: the batch contract at the top of this file for the whole call as if it were ONE batch: the final state is what the
+ *   reference reaches by applying those ops one by one in some order; values are exact (uint32, wrapping); row sizes and `used`
+ *   are the reference's -- into an empty dst, those of a matrix that never held the dropped pairs.  SET ties cannot occur:
+ *   every key occurs once.  Nothing beyond the batch contract is promised for the layout of a row's table.
+ * Bounded scratch: the work runs in internal batches of at most max(max_batch, longest SURVIVING row) ops -- max_batch == 0:
+ *   2^24; above 2^31: 2^31.  Device memory taken beyond the matrices is proportional to that bound plus 28 bytes per source ROW
+ *   (row list 8, kept count 4, scan 8, threshold 8), never to the number of pairs.  The result does not depend on max_batch in
+ *   anything the contract fixes (values, row set, sizes, `used`).
+ * Returns 0; -1 and nothing changed for: m == 0, an op other than SET / INCR / DECR, dst == src, the two matrices on different
+ *   devices.
+ * Locks and mirrors: both matrices' locks are held for the call, taken in address order; no file lock is taken.  Scalar writes
+ *   still in src's and dst's host mirrors are written back first and dst's mirror is dropped.  File-backed dst and src work
+ *   unchanged; smatrix_stats_t::batches counts the internal batches, and a call during which SMATRIX_FLUSH_EVERY falls due
+ *   takes ONE checkpoint, at its end.  src is not modified (its tables never shrink in place: build the truncated matrix, then
+ *   close the old one).  Runs on dst's own stream and returns when done. */
+int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint32_t min_value, uint64_t max_batch,
+                       uint64_t* n_ops, uint64_t* n_dropped);
 int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr,
                        const uint32_t* pairs, uint64_t max_batch, uint64_t* n_ops);
 int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows,

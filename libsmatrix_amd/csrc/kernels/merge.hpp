@@ -37,8 +37,10 @@ __device__ __forceinline__ void mg_put(uint32_t* __restrict__ rec, uint64_t at, 
   p[0] = x; p[1] = key; p[2] = val;
 }
 
+// (the walkers ask the functor for the predicate of row r of the row list, f.at(r): these two are the same for every row)
 struct MgIdent {
   __device__ __forceinline__ bool operator()(uint32_t, uint32_t&) const { return true; }
+  __device__ __forceinline__ const MgIdent& at(uint32_t) const { return *this; }
 };
 
 // floor(v * num / den) for 1 <= num <= den, exactly, without a 64-bit division.  n = v * num < 2^64 and the quotient is <= v.
@@ -63,13 +65,32 @@ struct MgScale {
     if (num != den) val = mg_scale_value(val, num, den, rden);
     return val >= min_value && (key | val) != 0;
   }
+  __device__ __forceinline__ const MgScale& at(uint32_t) const { return *this; }
+};
+
+// smatrix_merge_topk's filter: the pairs of row r whose rank key is at least thr[r] (k_mgt_select*, below), and the head pair.
+// mgt_key: larger is better -- by value, equal values by ascending column; unique within a row.
+__device__ __forceinline__ uint64_t mgt_key(uint32_t y, uint32_t v) { return ((uint64_t)v << 32) | (0xFFFFFFFFu - y); }
+
+struct MgTopkRow {
+  uint64_t thr;
+  uint32_t min_value;
+  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
+    if (val < min_value) return false;
+    return key == 0 ? val != 0 : mgt_key(key, val) >= thr;
+  }
+};
+struct MgTopk {
+  const uint64_t* thr;                                     // per row of the row list; 0 = every eligible pair
+  uint32_t min_value;
+  __device__ __forceinline__ MgTopkRow at(uint32_t r) const { return MgTopkRow{thr[r], min_value}; }
 };
 
 template <typename F>
 __device__ __forceinline__ void mg_emit_rows(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
                                              const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
                                              uint32_t* __restrict__ rec, uint32_t* big, const uint32_t wave, const uint32_t nwaves,
-                                             const F f) {
+                                             const F fn) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t lt = (1ull << lane) - 1;
   const uint64_t base = ptr[r0];
@@ -87,6 +108,7 @@ __device__ __forceinline__ void mg_emit_rows(const DirSlot* __restrict__ dir, ui
     }
     const uint4* cells = reinterpret_cast<const uint4*>(row_cells(arena, s.z));
     const uint32_t x = s.y;
+    const auto f = fn.at(r);
     uint64_t at = ptr[r] - base;
     auto fetch = [&](uint32_t p0) -> uint4 {
       const uint32_t p = p0 + 2 * lane;
@@ -130,7 +152,7 @@ __global__ __launch_bounds__(256) void k_mgx_emit(const DirSlot* __restrict__ di
 template <bool COUNT, typename F>
 __device__ __forceinline__ void mg_emit_segs(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
                                              const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
-                                             const uint32_t* big, uint32_t* seg_cnt, const F f) {
+                                             const uint32_t* big, uint32_t* seg_cnt, const F fn) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t s_written;
   const uint32_t nent = big[0];
@@ -156,6 +178,7 @@ __device__ __forceinline__ void mg_emit_segs(const DirSlot* __restrict__ dir, ui
     const uint8_t* cell_bytes = reinterpret_cast<const uint8_t*>(row_cells(arena, s.z));
     const uint4* cells = reinterpret_cast<const uint4*>(cell_bytes);
     const uint64_t first = (uint64_t)(cell_bytes - arena) >> MG_SEG_SHIFT;   // the row's first entry of seg_cnt
+    const auto f = fn.at(r);
     {
       const uint32_t p_begin = nseg == 1 ? 0u : g * GETROW_SEG, p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
       if (COUNT) {
@@ -281,6 +304,252 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
     }
     __syncthreads();
   }
+}
+
+// ---- the per-row selection of smatrix_merge_topk -------------------------------------------------------------------------------
+// thr[r] = the rank key of the m-th best ELIGIBLE pair of row r (y != 0, v >= min_value), or 0 when the row has at most m of them;
+// cnt[r] = the pairs the row keeps: min(m, eligible) + its head pair (y == 0) when v >= min_value.  MSB radix select on the 64-bit
+// key, 8 bits per pass, the 256 bins in LDS:
+//   pass 0      counts the eligible pairs and ORs their keys: a row of at most m is done, and the passes start at the highest
+//               byte that is not 0 in every key (small values: 3 passes less)
+//   a pass      re-reads the row (a wave-path row is at most 64 KiB and stays in L2) and counts, by their next byte, the keys
+//               that agree with the bytes chosen so far; the bins are walked from 255 down to the one that holds the key wanted
+//   the end     the last byte, or earlier when that bin holds ONE key: one more read of the row fetches it
+//   k_mgt_select       a wave per row of up to GETROW_WAVE_MAX cells (a histogram per wave: no workgroup barrier); longer rows are
+//                      noted in `big` (big[0] = entries, one row index each)
+//   k_mgt_select_big   those rows, ONE 1024-lane workgroup per row over all its segments -- they are few, and a histogram across
+//                      workgroups is not worth its launches
+// Both sum the non-empty cells they saw into *tot, as the k_mgx_count kernels do.  A cut row's seg_cnt entries are counted with
+// the finished threshold by k_mgt_emit_big<true>, batch by batch, as smatrix_merge does.
+__device__ __forceinline__ void mgt_wave_sync() {          // the LDS traffic of one wave, in program order for all its lanes
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ uint32_t mgt_wave_or(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
+__device__ __forceinline__ uint32_t mgt_wave_sum(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
+
+// one wave-wide step of a pass: hist[digit]++ for every lane with `match`.  Ties are the rule (equal values share the value
+// bytes), so the lanes that share the first matching lane's digit go in as one add.
+__device__ __forceinline__ void mgt_hist_add(uint32_t* hist, bool match, uint32_t digit, uint32_t lane) {
+  const uint64_t mm = __ballot(match);
+  if (mm == 0) return;
+  const uint32_t first = (uint32_t)__ffsll((unsigned long long)mm) - 1;
+  const uint32_t d0 = (uint32_t)__shfl((int)digit, (int)first);
+  const uint64_t same = __ballot(match && digit == d0);
+  if (lane == first) atomicAdd(&hist[d0], (uint32_t)__popcll(same));
+  if (match && digit != d0) atomicAdd(&hist[digit], 1u);
+}
+
+// one wave: the bin d that holds the need-th key counted from bin 255 down (1 <= need <= the sum of the bins), the keys in the
+// bins above d, and the keys in d -- to every lane.  Lane l holds bins 4 l .. 4 l + 3.
+// SERIAL: the bins of the lanes above come from 63 broadcast reads of LDS instead of a scan with shuffles -- the 1024-lane kernel
+// picks once per pass over a row of 128 KiB and more, and the scan's six lane tests, hoisted, are six SGPR pairs it has not got.
+template <bool SERIAL>
+__device__ __forceinline__ void mgt_pick(const uint32_t* hist, uint32_t need, uint32_t lane, uint32_t& d, uint32_t& above, uint32_t& bucket) {
+  const uint4 b = *reinterpret_cast<const uint4*>(hist + 4 * lane);
+  const uint32_t s = b.x + b.y + b.z + b.w;
+  uint32_t S = s;                                          // the bins of this lane and of the lanes above it
+  if (SERIAL) {
+#pragma unroll 1
+    for (uint32_t j = 1; j < 64; j++) {
+      const uint4 o = *reinterpret_cast<const uint4*>(hist + 4 * j);
+      if (j > lane) S += o.x + o.y + o.z + o.w;
+    }
+  } else {
+    for (uint32_t k = 1; k < 64; k <<= 1) { const uint32_t t = (uint32_t)__shfl_down((int)S, k); if (lane + k < 64) S += t; }
+  }
+  uint32_t a = S - s, dd = 3, bk = b.w;
+  const bool hit = a < need && need <= S;
+  if (need > a + b.w) {
+    a += b.w; dd = 2; bk = b.z;
+    if (need > a + b.z) {
+      a += b.z; dd = 1; bk = b.y;
+      if (need > a + b.y) { a += b.y; dd = 0; bk = b.x; }
+    }
+  }
+  const uint64_t hm = __ballot(hit);
+  const int src = hm ? __ffsll((unsigned long long)hm) - 1 : 0;
+  d = (uint32_t)__shfl((int)(4 * lane + dd), src);
+  above = (uint32_t)__shfl((int)a, src);
+  bucket = (uint32_t)__shfl((int)bk, src);
+}
+
+__device__ __forceinline__ bool mgt_eligible(uint32_t key, uint32_t val, uint32_t min_value) { return key != 0 && val >= min_value; }
+// (the shift is 56 at most; in two steps, so that 56 + 8 is no shift by 64)
+__device__ __forceinline__ bool mgt_agrees_above(uint64_t k, uint64_t prefix, uint32_t shift) { return (((k ^ prefix) >> shift) >> 8) == 0; }
+
+__global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ dir, uint8_t* arena, uint32_t n,
+                                                    const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value,
+                                                    uint64_t* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* big,
+                                                    unsigned long long* tot) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][256];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t* hist = s_hist[threadIdx.x >> 6];
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  uint32_t seen = 0;
+  for (uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n; r += nwaves) {
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
+    if (size > GETROW_WAVE_MAX) {
+      if (lane == 0) big[1 + atomicAdd(&big[0], 1u)] = r;
+      continue;
+    }
+    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
+    auto fetch = [&](uint32_t p0) -> uint4 {               // (every lane takes every step: the steps hold ballots)
+      const uint32_t p = p0 + 2 * lane;
+      return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
+    };
+    uint32_t elig = 0, head = 0, or_hi = 0, or_lo = 0;
+    for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+      const uint4 q = fetch(p0);
+      seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+      head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+      if (mgt_eligible(q.x, q.y, min_value)) { elig++; or_hi |= q.y; or_lo |= ~q.x; }
+      if (mgt_eligible(q.z, q.w, min_value)) { elig++; or_hi |= q.w; or_lo |= ~q.z; }
+    }
+    elig = mgt_wave_sum(elig);
+    head = mgt_wave_or(head);
+    uint64_t t = 0;
+    if (elig > m) {
+      const uint64_t orall = ((uint64_t)mgt_wave_or(or_hi) << 32) | mgt_wave_or(or_lo);   // (two keys and more: not 0)
+      uint32_t shift = (63u - (uint32_t)__clzll((long long)orall)) & ~7u, need = m;
+      uint64_t prefix = 0;
+      for (;;) {
+        for (uint32_t i = lane; i < 256; i += 64) hist[i] = 0;
+        mgt_wave_sync();
+        for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+          const uint4 q = fetch(p0);
+          const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
+          mgt_hist_add(hist, mgt_eligible(q.x, q.y, min_value) && mgt_agrees_above(k0, prefix, shift), (uint32_t)(k0 >> shift) & 255u, lane);
+          mgt_hist_add(hist, mgt_eligible(q.z, q.w, min_value) && mgt_agrees_above(k1, prefix, shift), (uint32_t)(k1 >> shift) & 255u, lane);
+        }
+        mgt_wave_sync();
+        uint32_t d, above, bucket;
+        mgt_pick<false>(hist, need, lane, d, above, bucket);
+        mgt_wave_sync();
+        need -= above;
+        prefix |= (uint64_t)d << shift;
+        if (shift == 0) { t = prefix; break; }
+        if (bucket == 1) {                                 // the one key that agrees down to this byte
+          uint32_t hi = 0, lo = 0;
+          for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+            const uint4 q = fetch(p0);
+            const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
+            if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
+            if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
+          }
+          t = ((uint64_t)mgt_wave_or(hi) << 32) | mgt_wave_or(lo);
+          break;
+        }
+        shift -= 8;
+      }
+    }
+    if (lane == 0) { thr[r] = t; cnt[r] = (elig < m ? elig : m) + head; }
+  }
+  seen = mgt_wave_sum(seen);
+  if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+}
+
+__global__ __launch_bounds__(1024) void k_mgt_select_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                         uint32_t m, uint32_t min_value, uint64_t* __restrict__ thr,
+                                                         uint32_t* __restrict__ cnt, const uint32_t* big, unsigned long long* tot) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ uint32_t wacc[5][16];                         // per wave: eligible, seen, head, OR of the keys (hi, lo)
+  __shared__ uint32_t acc[8];                              // 3, 4: the key found; 5 .. 7: d, above, bucket
+  auto uni = [&](uint32_t i) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)acc[i]); };   // (scalar control flow)
+  const uint32_t nent = big[0];
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t e = blockIdx.x; e < nent; e += gridDim.x) {
+    const uint32_t r = big[1 + e];
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = 1u << meta_lg(s.x);                          // > GETROW_WAVE_MAX: a multiple of 2048
+    const uint4* cells = reinterpret_cast<const uint4*>(row_cells(arena, s.z));
+    {
+      uint32_t elig = 0, seen = 0, head = 0, or_hi = 0, or_lo = 0;
+      for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+        const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+        seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+        head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+        if (mgt_eligible(q.x, q.y, min_value)) { elig++; or_hi |= q.y; or_lo |= ~q.x; }
+        if (mgt_eligible(q.z, q.w, min_value)) { elig++; or_hi |= q.w; or_lo |= ~q.z; }
+      }
+      elig = mgt_wave_sum(elig); seen = mgt_wave_sum(seen);
+      head = mgt_wave_or(head); or_hi = mgt_wave_or(or_hi); or_lo = mgt_wave_or(or_lo);
+      const uint32_t w = threadIdx.x >> 6;
+      if (lane == 0) { wacc[0][w] = elig; wacc[1][w] = seen; wacc[2][w] = head; wacc[3][w] = or_hi; wacc[4][w] = or_lo; }
+    }
+    __syncthreads();
+    uint32_t elig = 0, seen = 0, head = 0, or_hi = 0, or_lo = 0;
+    for (uint32_t i = 0; i < 16; i++) { elig += wacc[0][i]; seen += wacc[1][i]; head |= wacc[2][i]; or_hi |= wacc[3][i]; or_lo |= wacc[4][i]; }
+    elig = (uint32_t)__builtin_amdgcn_readfirstlane((int)elig);
+    const uint64_t orall = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)or_hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)or_lo);
+    if (threadIdx.x == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+    uint64_t t = 0;
+    if (elig > m) {                                                    // (from LDS: the same on every lane)
+      uint32_t shift = (63u - (uint32_t)__clzll((long long)orall)) & ~7u, need = m;
+      uint64_t prefix = 0;
+      for (;;) {
+        __syncthreads();                                               // (acc and hist were read by every lane)
+        if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+          const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+          const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
+          mgt_hist_add(hist, mgt_eligible(q.x, q.y, min_value) && mgt_agrees_above(k0, prefix, shift), (uint32_t)(k0 >> shift) & 255u, lane);
+          mgt_hist_add(hist, mgt_eligible(q.z, q.w, min_value) && mgt_agrees_above(k1, prefix, shift), (uint32_t)(k1 >> shift) & 255u, lane);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+          uint32_t d, above, bucket;
+          mgt_pick<true>(hist, need, lane, d, above, bucket);
+          if (lane == 0) { acc[5] = d; acc[6] = above; acc[7] = bucket; }
+        }
+        __syncthreads();
+        need -= uni(6);
+        prefix |= (uint64_t)uni(5) << shift;
+        if (shift == 0) { t = prefix; break; }
+        if (uni(7) == 1) {
+          if (threadIdx.x < 2) acc[3 + threadIdx.x] = 0;
+          __syncthreads();
+          uint32_t hi = 0, lo = 0;
+          for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+            const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+            const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
+            if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
+            if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
+          }
+          if (hi | lo) { acc[3] = hi; acc[4] = lo; }                     // (one lane of the workgroup: keys are unique)
+          __syncthreads();
+          t = ((uint64_t)acc[3] << 32) | acc[4];
+          break;
+        }
+        shift -= 8;
+      }
+    }
+    if (threadIdx.x == 0) { thr[r] = t; cnt[r] = (elig < m ? elig : m) + head; }
+    __syncthreads();                                                   // (wacc and acc are the next row's)
+  }
+}
+
+// the emission of smatrix_merge_topk: the walkers above with the per-row threshold
+__global__ __launch_bounds__(256) void k_mgt_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgTopk f) {
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, f);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mgt_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                       const uint32_t* big, uint32_t* seg_cnt, const MgTopk f) {
+  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
 }
 
 // ---- from a CSR in smatrix_export's layout ------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h),
+// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h),
 // host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_measure and scan);
 // the device code is kernels/merge.hpp.
@@ -15,6 +15,8 @@
 // the source 8 (row list) + 4 (counts) + 8 (scan) bytes -- nothing per pair.
 // merge_scaled: merge with the counts of the SURVIVORS of its transform (k_mgx_count*, instead of the export's k_ex_count*) under
 //        the same scan, so the cuts and the rows' record offsets are those of what k_mgx_emit* will write; same memory.
+// merge_topk: the same with the counts and an 8-byte threshold per row from the selection (k_mgt_select*); the emission filters
+//        by that threshold (k_mgt_emit*) and counts a cut row's segments batch by batch, as merge does.  28 bytes per row.
 
 namespace {
 
@@ -23,7 +25,7 @@ constexpr uint64_t MG_MAX_BATCH = 1ull << 31;          // (a write batch holds f
 
 struct MergeScratch {
   DevBuf<uint32_t> rec[2], big, seg_cnt, flag, h_rows, h_pairs[2];
-  DevBuf<uint64_t> ptr, h_ptr;
+  DevBuf<uint64_t> ptr, h_ptr, thr;                      // thr: merge_topk's per-row rank-key thresholds
   DevBuf<unsigned long long> tot;                        // merge_scaled: the candidates the count kernels saw
   hipStream_t e = nullptr;                               // the helper stream: emission
   hipEvent_t ev_start = nullptr, ev_rec[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
@@ -46,7 +48,7 @@ MergeScratch& mg_of(Matrix* m) {
 void mg_trim_all(MergeScratch& g, bool all) {
   ex_trim(g.rec[0], all); ex_trim(g.rec[1], all); ex_trim(g.big, all); ex_trim(g.seg_cnt, all); ex_trim(g.flag, all);
   ex_trim(g.h_rows, all); ex_trim(g.h_pairs[0], all); ex_trim(g.h_pairs[1], all); ex_trim(g.ptr, all); ex_trim(g.h_ptr, all);
-  ex_trim(g.tot, all);
+  ex_trim(g.tot, all); ex_trim(g.thr, all);
 }
 
 void merge_release(Matrix* m) {
@@ -271,6 +273,75 @@ int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, u
         hipLaunchKernelGGL(k_mgx_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
                            sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p, f);
         hipLaunchKernelGGL(k_mgx_emit_big, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                           r0, rec, g.big.p, g.seg_cnt.p, f);
+      });
+    }
+  }
+  HIP_OK(hipStreamSynchronize(s));
+  if (n_ops) *n_ops = kept;
+  if (n_dropped) *n_dropped = seen - kept;
+  ex_trim_all(x, false);
+  mg_trim_all(g, false);
+  return 0;
+}
+
+int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint32_t min_value, uint64_t max_batch, uint64_t* n_ops,
+                       uint64_t* n_dropped) {
+  if (!mg_op_ok(op) || !dst || !src || dst == src || m == 0) return -1;
+  Matrix *d = M(dst), *sm = M(src);
+  if (d == sm || d->device != sm->device) return -1;
+  set_device(d);
+  CkptAfter ckpt(dst);
+  std::unique_lock<std::mutex> l0(d < sm ? d->mu : sm->mu);   // (locks, mirrors, stream: as smatrix_merge)
+  std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
+  cache_sync(sm, false);
+  cache_sync(d, true);
+  hipStream_t s = d->stream;
+  ExportScratch& x = ex_of(sm);
+  MergeScratch& g = mg_of(d);
+  const uint64_t n = ex_row_list(sm, x, SMATRIX_EXPORT_TABLE, s);
+  uint64_t kept = 0;
+  unsigned long long seen = 0;
+  if (n) {
+    // the selection: every row's threshold and, with it, the number of pairs the row keeps -- the count of an uncut row needs
+    // no pass of its own.  `big` lists the rows of more than GETROW_WAVE_MAX cells here (one word each: it has room for two per
+    // 128 KiB of row tables, and such a row is 128 KiB at least); the emission of every batch starts it afresh.
+    x.cnt.need(n);
+    g.thr.need(n);
+    mg_need_big(g, sm);
+    g.tot.need(1);
+    const uint32_t big_grid = mg_big_grid(sm);
+    HIP_OK(hipMemsetAsync(g.big.p, 0, 4, s));
+    HIP_OK(hipMemsetAsync(g.tot.p, 0, 8, s));
+    hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
+    if (d->profile) { for (hipEvent_t& ev : tev) HIP_OK(hipEventCreate(&ev)); HIP_OK(hipEventRecord(tev[0], s)); }
+    hipLaunchKernelGGL(k_mgt_select, dim3(std::min<uint32_t>(blocks_for(n * 64), 16384)), dim3(256), 0, s, sm->d_dir, sm->arena.base,
+                       (uint32_t)n, x.items.p, m, min_value, g.thr.p, x.cnt.p, g.big.p, g.tot.p);
+    hipLaunchKernelGGL(k_mgt_select_big, dim3(big_grid), dim3(1024), 0, s, sm->d_dir, sm->arena.base, x.items.p, m, min_value,
+                       g.thr.p, x.cnt.p, g.big.p, g.tot.p);
+    HIP_OK(hipGetLastError());
+    if (d->profile) HIP_OK(hipEventRecord(tev[1], s));
+    x.cnt_tiles = ex_scan_prep(x, s, x.cnt.p, n);
+    if (d->profile) HIP_OK(hipEventRecord(tev[2], s));
+    HIP_OK(hipMemcpyAsync(&seen, g.tot.p, 8, hipMemcpyDeviceToHost, s));
+    kept = ex_read(x.part.p + x.cnt_tiles, s);
+    if (d->profile) {
+      float sel = 0, cnt = 0;
+      HIP_OK(hipEventElapsedTime(&sel, tev[0], tev[1]));
+      HIP_OK(hipEventElapsedTime(&cnt, tev[1], tev[2]));
+      for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
+      fprintf(stderr, "[smatrix] merge_topk: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
+              sel, cnt, (unsigned long long)kept, seen);
+    }
+    if (kept) {
+      const MgTopk f{g.thr.p, min_value};
+      mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+        HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
+        hipLaunchKernelGGL(k_mgt_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
+                           sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p, f);
+        hipLaunchKernelGGL(k_mgt_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
+                           r0, rec, g.big.p, g.seg_cnt.p, f);
+        hipLaunchKernelGGL(k_mgt_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
                            r0, rec, g.big.p, g.seg_cnt.p, f);
       });
     }

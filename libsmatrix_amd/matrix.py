@@ -46,6 +46,13 @@ def _scale_args(num, den, min_value):
         raise ValueError("1 <= num <= den is required, not %r / %r" % (num, den))
 
 
+def _topk_args(m, min_value):
+    """merge_topk's m / min_value: uint32 each, m >= 1; anything else is a ValueError"""
+    for name, val, lo in (("m", m, 1), ("min_value", min_value, 0)):
+        if not isinstance(val, (int, np.integer)) or isinstance(val, bool) or not lo <= val <= 0xFFFFFFFF:
+            raise ValueError("%s must be an integer in %d .. 2**32 - 1, not %r" % (name, lo, val))
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -359,6 +366,33 @@ class SparseMatrix:
             m.close()
             raise
         return m
+
+    def merge_topk(self, other, m, op="set", min_value=1, max_batch=0):
+        """merge that keeps the m heaviest pairs of every row of other: of the pairs (y != 0, v >= min_value) those of the largest
+        v, equal values by ascending column; the column-0 pair (the CF total) is kept beside them when v >= min_value.  The kept
+        pairs are applied as self[x, y] op= v.  1 <= m <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified."""
+        o = _merge_op(op)
+        _topk_args(m, min_value)
+        if not isinstance(other, SparseMatrix):
+            raise TypeError("merge_topk needs another SparseMatrix, not %r" % (type(other).__name__,))
+        n, dropped = C.c_uint64(0), C.c_uint64(0)
+        if self._lib.smatrix_merge_topk(self._h, other._h, o, int(m), int(min_value), int(max_batch),
+                                        C.byref(n), C.byref(dropped)) != 0:
+            raise ValueError("smatrix_merge_topk refused: a matrix cannot be merged into itself, and both must be on one device")
+        return n.value, dropped.value
+
+    def truncated(self, m, min_value=1, filename=None):
+        """a NEW matrix (in memory, or file-backed when filename is given) that holds, of every row of self, the m heaviest pairs
+        of at least min_value and the column-0 pair: at most m + 1 pairs per row, the serving copy of an item-kNN recommender
+        (total += today; total -= day_30; serving = total.truncated(m)).  self is not modified."""
+        _topk_args(m, min_value)
+        m_new = SparseMatrix(filename)
+        try:
+            m_new.merge_topk(self, m, "set", min_value)
+        except Exception:
+            m_new.close()
+            raise
+        return m_new
 
     def __iadd__(self, other):
         if not isinstance(other, SparseMatrix):
