@@ -37,6 +37,21 @@ __device__ __forceinline__ void mg_put(uint32_t* __restrict__ rec, uint64_t at, 
   p[0] = x; p[1] = key; p[2] = val;
 }
 
+__device__ __forceinline__ uint32_t mg_wave_or(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
+__device__ __forceinline__ uint32_t mg_wave_sum(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
+
+// the cells [p_begin, p_end) of segment g of a row of nseg segments (an uncut row of any size is its one segment)
+__device__ __forceinline__ void mg_seg_range(uint32_t size, uint32_t nseg, uint32_t g, uint32_t& p_begin, uint32_t& p_end) {
+  p_begin = nseg == 1 ? 0u : g * GETROW_SEG;
+  p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
+}
+
 // (the walkers ask the functor for the predicate of row r of the row list, f.at(r): these two are the same for every row)
 struct MgIdent {
   __device__ __forceinline__ bool operator()(uint32_t, uint32_t&) const { return true; }
@@ -160,7 +175,7 @@ __device__ __forceinline__ void mg_emit_segs(const DirSlot* __restrict__ dir, ui
   const uint64_t lt = (1ull << lane) - 1;
   const uint64_t base = ptr[r0];
   auto block_sum = [&](uint32_t v) -> uint32_t {          // sum over the workgroup, to every lane
-    for (uint32_t d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    v = mg_wave_sum(v);
     __syncthreads();
     if (lane == 0) wsum[w] = v;
     __syncthreads();
@@ -180,7 +195,8 @@ __device__ __forceinline__ void mg_emit_segs(const DirSlot* __restrict__ dir, ui
     const uint64_t first = (uint64_t)(cell_bytes - arena) >> MG_SEG_SHIFT;   // the row's first entry of seg_cnt
     const auto f = fn.at(r);
     {
-      const uint32_t p_begin = nseg == 1 ? 0u : g * GETROW_SEG, p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
+      uint32_t p_begin, p_end;
+      mg_seg_range(size, nseg, g, p_begin, p_end);
       if (COUNT) {
         uint32_t c = 0;
         for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
@@ -266,7 +282,7 @@ __global__ __launch_bounds__(256) void k_mgx_count(const DirSlot* __restrict__ d
     for (uint32_t d = 32; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
     if (lane == 0) cnt[r] = c;
   }
-  for (uint32_t d = 32; d; d >>= 1) seen += (uint32_t)__shfl_xor((int)seen, d);   // (a wave's rows hold < 2^32 cells: rows * 8192 / waves)
+  seen = mg_wave_sum(seen);                                            // (a wave's rows hold < 2^32 cells: rows * 8192 / waves)
   if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
 }
 
@@ -283,7 +299,8 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
     const uint32_t nseg = getrow_nseg(size);
     const uint8_t* cell_bytes = reinterpret_cast<const uint8_t*>(row_cells(arena, s.z));
     const uint4* cells = reinterpret_cast<const uint4*>(cell_bytes);
-    const uint32_t p_begin = nseg == 1 ? 0u : g * GETROW_SEG, p_end = nseg == 1 ? size : p_begin + GETROW_SEG;
+    uint32_t p_begin, p_end;
+    mg_seg_range(size, nseg, g, p_begin, p_end);
     uint32_t c = 0, seen = 0;
     for (uint32_t p0 = p_begin; p0 < p_end; p0 += 2048) {
       uint4 q = cells[(p0 >> 1) + threadIdx.x];
@@ -291,6 +308,7 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
       seen += ne0 + ne1;
       c += (ne0 && f(q.x, q.y)) + (ne1 && f(q.z, q.w));
     }
+    // (spelled out here and in k_mgx_count's loop: through mg_wave_sum these two kernels come out scheduled differently)
     for (uint32_t d = 32; d; d >>= 1) { c += (uint32_t)__shfl_xor((int)c, d); seen += (uint32_t)__shfl_xor((int)seen, d); }
     if (lane == 0) { wsum[0][w] = c; wsum[1][w] = seen; }
     __syncthreads();
@@ -324,15 +342,6 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
 __device__ __forceinline__ void mgt_wave_sync() {          // the LDS traffic of one wave, in program order for all its lanes
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint32_t mgt_wave_or(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
-__device__ __forceinline__ uint32_t mgt_wave_sum(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  return v;
 }
 
 // one wave-wide step of a pass: hist[digit]++ for every lane with `match`.  Ties are the rule (equal values share the value
@@ -385,6 +394,13 @@ __device__ __forceinline__ bool mgt_eligible(uint32_t key, uint32_t val, uint32_
 // (the shift is 56 at most; in two steps, so that 56 + 8 is no shift by 64)
 __device__ __forceinline__ bool mgt_agrees_above(uint64_t k, uint64_t prefix, uint32_t shift) { return (((k ^ prefix) >> shift) >> 8) == 0; }
 
+// the end, when one key agrees with the prefix down to `shift`: that key, ORed into (hi, lo), if it is one of the two cells in q
+__device__ __forceinline__ void mgt_fetch_key(const uint4 q, uint32_t min_value, uint64_t prefix, uint32_t shift, uint32_t& hi, uint32_t& lo) {
+  const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
+  if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
+  if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
+}
+
 __global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ dir, uint8_t* arena, uint32_t n,
                                                     const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value,
                                                     uint64_t* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* big,
@@ -414,11 +430,11 @@ __global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ 
       if (mgt_eligible(q.x, q.y, min_value)) { elig++; or_hi |= q.y; or_lo |= ~q.x; }
       if (mgt_eligible(q.z, q.w, min_value)) { elig++; or_hi |= q.w; or_lo |= ~q.z; }
     }
-    elig = mgt_wave_sum(elig);
-    head = mgt_wave_or(head);
+    elig = mg_wave_sum(elig);
+    head = mg_wave_or(head);
     uint64_t t = 0;
     if (elig > m) {
-      const uint64_t orall = ((uint64_t)mgt_wave_or(or_hi) << 32) | mgt_wave_or(or_lo);   // (two keys and more: not 0)
+      const uint64_t orall = ((uint64_t)mg_wave_or(or_hi) << 32) | mg_wave_or(or_lo);   // (two keys and more: not 0)
       uint32_t shift = (63u - (uint32_t)__clzll((long long)orall)) & ~7u, need = m;
       uint64_t prefix = 0;
       for (;;) {
@@ -439,13 +455,8 @@ __global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ 
         if (shift == 0) { t = prefix; break; }
         if (bucket == 1) {                                 // the one key that agrees down to this byte
           uint32_t hi = 0, lo = 0;
-          for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-            const uint4 q = fetch(p0);
-            const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
-            if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
-            if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
-          }
-          t = ((uint64_t)mgt_wave_or(hi) << 32) | mgt_wave_or(lo);
+          for (uint32_t p0 = 0; p0 < size; p0 += 128) mgt_fetch_key(fetch(p0), min_value, prefix, shift, hi, lo);
+          t = ((uint64_t)mg_wave_or(hi) << 32) | mg_wave_or(lo);
           break;
         }
         shift -= 8;
@@ -453,7 +464,7 @@ __global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ 
     }
     if (lane == 0) { thr[r] = t; cnt[r] = (elig < m ? elig : m) + head; }
   }
-  seen = mgt_wave_sum(seen);
+  seen = mg_wave_sum(seen);
   if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
 }
 
@@ -480,8 +491,8 @@ __global__ __launch_bounds__(1024) void k_mgt_select_big(const DirSlot* __restri
         if (mgt_eligible(q.x, q.y, min_value)) { elig++; or_hi |= q.y; or_lo |= ~q.x; }
         if (mgt_eligible(q.z, q.w, min_value)) { elig++; or_hi |= q.w; or_lo |= ~q.z; }
       }
-      elig = mgt_wave_sum(elig); seen = mgt_wave_sum(seen);
-      head = mgt_wave_or(head); or_hi = mgt_wave_or(or_hi); or_lo = mgt_wave_or(or_lo);
+      elig = mg_wave_sum(elig); seen = mg_wave_sum(seen);
+      head = mg_wave_or(head); or_hi = mg_wave_or(or_hi); or_lo = mg_wave_or(or_lo);
       const uint32_t w = threadIdx.x >> 6;
       if (lane == 0) { wacc[0][w] = elig; wacc[1][w] = seen; wacc[2][w] = head; wacc[3][w] = or_hi; wacc[4][w] = or_lo; }
     }
@@ -519,12 +530,7 @@ __global__ __launch_bounds__(1024) void k_mgt_select_big(const DirSlot* __restri
           if (threadIdx.x < 2) acc[3 + threadIdx.x] = 0;
           __syncthreads();
           uint32_t hi = 0, lo = 0;
-          for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
-            const uint4 q = cells[(p0 >> 1) + threadIdx.x];
-            const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
-            if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
-            if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
-          }
+          for (uint32_t p0 = 0; p0 < size; p0 += 2048) mgt_fetch_key(cells[(p0 >> 1) + threadIdx.x], min_value, prefix, shift, hi, lo);
           if (hi | lo) { acc[3] = hi; acc[4] = lo; }                     // (one lane of the workgroup: keys are unique)
           __syncthreads();
           t = ((uint64_t)acc[3] << 32) | acc[4];

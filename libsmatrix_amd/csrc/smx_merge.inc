@@ -1,9 +1,13 @@
 // smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h),
 // host side.
-// Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_measure and scan);
-// the device code is kernels/merge.hpp.
+// Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_row_list, ex_measure
+// and scan); the device code is kernels/merge.hpp.
 //
-// Both calls are one loop over INTERNAL BATCHES of at most `bound` ops: a kernel writes batch b's packed {x, y, v} records into
+// The three merges are one driver, mg_merge (validation, both locks, the mirrors, the scratch, the end of the call), around two
+// stages that the entry point hands it: a count stage that leaves every row's count in x.cnt (ex_measure; for the filtered
+// flavours mg_count_filtered around their own kernels) and an emit stage that mg_run_rows calls batch by batch.
+//
+// Every call is one loop over INTERNAL BATCHES of at most `bound` ops: a kernel writes batch b's packed {x, y, v} records into
 // one of two record buffers, the ordinary write path applies them (run_write with in_stride == 3 and no result array, as
 // smatrix_apply_packed_dev does), batches in order.  Batch b + 1 is emitted on a helper stream while the rounds of batch b run:
 //   helper:  emit(0)  emit(1)         emit(2)          ...        (emit(b) waits for the write of batch b - 2: same buffer)
@@ -145,9 +149,9 @@ int mg_import(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows, 
   return 0;
 }
 
-// merge / merge_scaled once the counts of the source's n rows are in x.cnt and the first half of their scan is done
-// (x.cnt_tiles): the second half, the batches cut on the host, the loop.  emit(r0, r1, rec, e) enqueues the kernels that write
-// the records of the rows [r0, r1) of the row list on stream e.  The caller holds both locks.
+// the merges once the counts of the source's n rows are in x.cnt and the first half of their scan is done (x.cnt_tiles): the
+// second half, the batches cut on the host, the loop.  emit(r0, r1, rec, e) enqueues the kernels that write the records of the
+// rows [r0, r1) of the row list on stream e.  The caller holds both locks.
 template <typename EmitRows>
 void mg_run_rows(smatrix_t* dst, ExportScratch& x, MergeScratch& g, int op, hipStream_t s, uint64_t n, uint64_t max_batch, EmitRows emit) {
   g.ptr.need(n + 1);
@@ -181,13 +185,40 @@ void mg_need_big(MergeScratch& g, Matrix* sm) {
   g.big.need(2 * ((sm->arena.mapped >> 17) + (sm->arena.mapped >> MG_SEG_SHIFT) + 2) + 1);
   g.seg_cnt.need((sm->arena.mapped >> MG_SEG_SHIFT) + 2);
 }
-uint32_t mg_big_grid(Matrix* sm) { return (uint32_t)std::min<uint64_t>(sm->arena.mapped / 8 / GETROW_SEG + 1, 2048); }
+uint32_t mg_row_grid(uint64_t rows) { return std::min<uint32_t>(blocks_for(rows * 64), 16384); }   // the wave-per-row kernels
 
-}  // namespace
+// One call of the merge family, between its stages: both matrices (locked), the destination's stream, the source's export
+// scratch, the destination's merge scratch; from the count stage on, the rows of the source's row list (x.items), the pairs the
+// call applies and, in the filtered flavours, the pairs it looked at.
+struct MergeCall {
+  Matrix *d, *sm;
+  hipStream_t s;
+  ExportScratch& x;
+  MergeScratch& g;
+  uint32_t big_grid;                                       // of the 1024-lane kernels that walk `big`
+  uint64_t n = 0, kept = 0;
+  unsigned long long seen = 0;
+};
 
-extern "C" {
+// the wave-per-row / per-segment launch of an emission: the kernel's common arguments, then the flavour's functor (if any)
+template <typename K, typename... F>
+void mg_emit(const MergeCall& c, K kernel, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e, F... f) {
+  hipLaunchKernelGGL(kernel, dim3(mg_row_grid(r1 - r0)), dim3(256), 0, e, c.sm->d_dir, c.sm->arena.base, c.x.items.p, c.g.ptr.p,
+                     r0, r1, rec, c.g.big.p, f...);
+}
+template <typename K, typename... F>
+void mg_emit_big(const MergeCall& c, K kernel, uint32_t r0, uint32_t* rec, hipStream_t e, F... f) {
+  hipLaunchKernelGGL(kernel, dim3(c.big_grid), dim3(1024), 0, e, c.sm->d_dir, c.sm->arena.base, c.x.items.p, c.g.ptr.p,
+                     r0, rec, c.g.big.p, c.g.seg_cnt.p, f...);
+}
 
-int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops) {
+// The driver of smatrix_merge / _scaled / _topk, behind the flavour's own validation clause.
+//   count(c)                  leaves c.n, every row's count in c.x.cnt, c.x.cnt_tiles (ex_scan_prep), c.kept and c.seen; when
+//                             c.kept != 0 also `big` and seg_cnt sized (mg_need_big)
+//   emit(c, r0, r1, rec, e)   enqueues the kernels that write the records of the rows [r0, r1) on stream e; big[0] is 0
+// Refusals come before any lock or device call; n_dropped is NULL where the flavour drops nothing.
+template <typename Count, typename Emit>
+int mg_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped, Count count, Emit emit) {
   if (!mg_op_ok(op) || !dst || !src || dst == src) return -1;
   Matrix *d = M(dst), *sm = M(src);
   if (d == sm || d->device != sm->device) return -1;
@@ -199,159 +230,124 @@ int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, ui
   std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
   cache_sync(sm, false);
   cache_sync(d, true);
-  hipStream_t s = d->stream;
-  ExportScratch& x = ex_of(sm);
-  MergeScratch& g = mg_of(d);
-  uint64_t n = 0, nnz = 0;
-  ex_measure(sm, x, SMATRIX_EXPORT_TABLE, s, &n, &nnz);   // the row list, the counts, the first half of their scan
-  if (nnz) {
-    mg_need_big(g, sm);
-    const uint32_t big_grid = mg_big_grid(sm);
-    mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
-      HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
-      hipLaunchKernelGGL(k_mg_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
-                         sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p);
-      hipLaunchKernelGGL(k_mg_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                         r0, rec, g.big.p, g.seg_cnt.p);
-      hipLaunchKernelGGL(k_mg_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                         r0, rec, g.big.p, g.seg_cnt.p);
+  MergeCall c{d, sm, d->stream, ex_of(sm), mg_of(d), (uint32_t)std::min<uint64_t>(sm->arena.mapped / 8 / GETROW_SEG + 1, 2048)};
+  count(c);
+  if (c.kept)
+    mg_run_rows(dst, c.x, c.g, op, c.s, c.n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      HIP_OK(hipMemsetAsync(c.g.big.p, 0, 4, e));
+      emit(c, r0, r1, rec, e);
     });
-  }
-  HIP_OK(hipStreamSynchronize(s));
-  if (n_ops) *n_ops = nnz;
-  ex_trim_all(x, false);
-  mg_trim_all(g, false);
+  HIP_OK(hipStreamSynchronize(c.s));
+  if (n_ops) *n_ops = c.kept;
+  if (n_dropped) *n_dropped = c.seen - c.kept;
+  ex_trim_all(c.x, false);
+  mg_trim_all(c.g, false);
   return 0;
+}
+
+// The count stage of the filtered flavours (what ex_measure is to smatrix_merge): the row list; `launch` enqueues the kernels
+// that leave every row's survivors in x.cnt and the non-empty cells they saw in *g.tot (with `big` started at 0 entries); the
+// first half of the scan; both totals read back.  A profiled matrix times the kernels, and the scan when scan_timed, with HIP
+// events: report(kernels_ms, scan_ms) prints the flavour's stderr line.
+template <typename Launch, typename Report>
+void mg_count_filtered(MergeCall& c, bool scan_timed, Launch launch, Report report) {
+  ExportScratch& x = c.x;
+  MergeScratch& g = c.g;
+  hipStream_t s = c.s;
+  c.n = ex_row_list(c.sm, x, SMATRIX_EXPORT_TABLE, s);
+  if (!c.n) return;
+  x.cnt.need(c.n);
+  mg_need_big(g, c.sm);
+  g.tot.need(1);
+  HIP_OK(hipMemsetAsync(g.big.p, 0, 4, s));
+  HIP_OK(hipMemsetAsync(g.tot.p, 0, 8, s));
+  const bool timed = c.d->profile;
+  hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
+  if (timed) { for (hipEvent_t& ev : tev) HIP_OK(hipEventCreate(&ev)); HIP_OK(hipEventRecord(tev[0], s)); }
+  launch();
+  HIP_OK(hipGetLastError());
+  if (timed) HIP_OK(hipEventRecord(tev[1], s));
+  x.cnt_tiles = ex_scan_prep(x, s, x.cnt.p, c.n);
+  if (timed && scan_timed) HIP_OK(hipEventRecord(tev[2], s));
+  HIP_OK(hipMemcpyAsync(&c.seen, g.tot.p, 8, hipMemcpyDeviceToHost, s));
+  c.kept = ex_read(x.part.p + x.cnt_tiles, s);
+  if (timed) {
+    float kernels = 0, scan = 0;
+    HIP_OK(hipEventElapsedTime(&kernels, tev[0], tev[1]));
+    if (scan_timed) HIP_OK(hipEventElapsedTime(&scan, tev[1], tev[2]));
+    for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
+    report(kernels, scan);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int smatrix_merge(smatrix_t* dst, smatrix_t* src, int op, uint64_t max_batch, uint64_t* n_ops) {
+  return mg_merge(dst, src, op, max_batch, n_ops, nullptr,
+    [](MergeCall& c) {                                    // the row list, the counts, the first half of their scan
+      ex_measure(c.sm, c.x, SMATRIX_EXPORT_TABLE, c.s, &c.n, &c.kept);
+      if (c.kept) mg_need_big(c.g, c.sm);
+    },
+    [](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      mg_emit(c, k_mg_emit, r0, r1, rec, e);
+      mg_emit_big(c, k_mg_emit_big<true>, r0, rec, e);
+      mg_emit_big(c, k_mg_emit_big<false>, r0, rec, e);
+    });
 }
 
 int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, uint32_t den, uint32_t min_value, uint64_t max_batch,
                          uint64_t* n_ops, uint64_t* n_dropped) {
-  if (!mg_op_ok(op) || !dst || !src || dst == src || num == 0 || num > den) return -1;    // (num >= 1, so den == 0 is num > den)
-  Matrix *d = M(dst), *sm = M(src);
-  if (d == sm || d->device != sm->device) return -1;
-  set_device(d);
-  CkptAfter ckpt(dst);
-  std::unique_lock<std::mutex> l0(d < sm ? d->mu : sm->mu);   // (locks, mirrors, stream: as smatrix_merge)
-  std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
-  cache_sync(sm, false);
-  cache_sync(d, true);
-  hipStream_t s = d->stream;
-  ExportScratch& x = ex_of(sm);
-  MergeScratch& g = mg_of(d);
+  if (num == 0 || num > den) return -1;                   // (num >= 1, so den == 0 is num > den)
   const MgScale f{num, den, min_value, 1.0 / (double)den};
-  const uint64_t n = ex_row_list(sm, x, SMATRIX_EXPORT_TABLE, s);
-  uint64_t kept = 0;
-  unsigned long long seen = 0;
-  if (n) {
-    // the survivors of every row (and of every segment of a cut row) and the candidates in all: the one counting pass
-    x.cnt.need(n);
-    mg_need_big(g, sm);
-    g.tot.need(1);
-    const uint32_t big_grid = mg_big_grid(sm);
-    HIP_OK(hipMemsetAsync(g.big.p, 0, 4, s));
-    HIP_OK(hipMemsetAsync(g.tot.p, 0, 8, s));
-    hipEvent_t tev[2] = {nullptr, nullptr};
-    if (d->profile) { for (hipEvent_t& ev : tev) HIP_OK(hipEventCreate(&ev)); HIP_OK(hipEventRecord(tev[0], s)); }
-    hipLaunchKernelGGL(k_mgx_count, dim3(std::min<uint32_t>(blocks_for(n * 64), 16384)), dim3(256), 0, s, sm->d_dir, sm->arena.base,
-                       (uint32_t)n, x.items.p, x.cnt.p, g.big.p, g.tot.p, f);
-    hipLaunchKernelGGL(k_mgx_count_big, dim3(big_grid), dim3(1024), 0, s, sm->d_dir, sm->arena.base, x.items.p, x.cnt.p, g.big.p,
-                       g.seg_cnt.p, g.tot.p, f);
-    HIP_OK(hipGetLastError());
-    if (d->profile) HIP_OK(hipEventRecord(tev[1], s));
-    x.cnt_tiles = ex_scan_prep(x, s, x.cnt.p, n);
-    HIP_OK(hipMemcpyAsync(&seen, g.tot.p, 8, hipMemcpyDeviceToHost, s));
-    kept = ex_read(x.part.p + x.cnt_tiles, s);
-    if (d->profile) {
-      float ms = 0;
-      HIP_OK(hipEventElapsedTime(&ms, tev[0], tev[1]));
-      for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
-      fprintf(stderr, "[smatrix] merge_scaled: filtered count %.3f ms, %llu of %llu pairs survive\n", ms, (unsigned long long)kept, seen);
-    }
-    if (kept) {
-      mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
-        HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
-        hipLaunchKernelGGL(k_mgx_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
-                           sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p, f);
-        hipLaunchKernelGGL(k_mgx_emit_big, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                           r0, rec, g.big.p, g.seg_cnt.p, f);
-      });
-    }
-  }
-  HIP_OK(hipStreamSynchronize(s));
-  if (n_ops) *n_ops = kept;
-  if (n_dropped) *n_dropped = seen - kept;
-  ex_trim_all(x, false);
-  mg_trim_all(g, false);
-  return 0;
+  return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
+    [&](MergeCall& c) {
+      // the survivors of every row (and of every segment of a cut row) and the candidates in all: the one counting pass
+      mg_count_filtered(c, false,
+        [&] {
+          hipLaunchKernelGGL(k_mgx_count, dim3(mg_row_grid(c.n)), dim3(256), 0, c.s, c.sm->d_dir, c.sm->arena.base, (uint32_t)c.n,
+                             c.x.items.p, c.x.cnt.p, c.g.big.p, c.g.tot.p, f);
+          hipLaunchKernelGGL(k_mgx_count_big, dim3(c.big_grid), dim3(1024), 0, c.s, c.sm->d_dir, c.sm->arena.base, c.x.items.p,
+                             c.x.cnt.p, c.g.big.p, c.g.seg_cnt.p, c.g.tot.p, f);
+        },
+        [&](float ms, float) {
+          fprintf(stderr, "[smatrix] merge_scaled: filtered count %.3f ms, %llu of %llu pairs survive\n", ms, (unsigned long long)c.kept, c.seen);
+        });
+    },
+    [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      mg_emit(c, k_mgx_emit, r0, r1, rec, e, f);
+      mg_emit_big(c, k_mgx_emit_big, r0, rec, e, f);
+    });
 }
 
 int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint32_t min_value, uint64_t max_batch, uint64_t* n_ops,
                        uint64_t* n_dropped) {
-  if (!mg_op_ok(op) || !dst || !src || dst == src || m == 0) return -1;
-  Matrix *d = M(dst), *sm = M(src);
-  if (d == sm || d->device != sm->device) return -1;
-  set_device(d);
-  CkptAfter ckpt(dst);
-  std::unique_lock<std::mutex> l0(d < sm ? d->mu : sm->mu);   // (locks, mirrors, stream: as smatrix_merge)
-  std::unique_lock<std::mutex> l1(d < sm ? sm->mu : d->mu);
-  cache_sync(sm, false);
-  cache_sync(d, true);
-  hipStream_t s = d->stream;
-  ExportScratch& x = ex_of(sm);
-  MergeScratch& g = mg_of(d);
-  const uint64_t n = ex_row_list(sm, x, SMATRIX_EXPORT_TABLE, s);
-  uint64_t kept = 0;
-  unsigned long long seen = 0;
-  if (n) {
-    // the selection: every row's threshold and, with it, the number of pairs the row keeps -- the count of an uncut row needs
-    // no pass of its own.  `big` lists the rows of more than GETROW_WAVE_MAX cells here (one word each: it has room for two per
-    // 128 KiB of row tables, and such a row is 128 KiB at least); the emission of every batch starts it afresh.
-    x.cnt.need(n);
-    g.thr.need(n);
-    mg_need_big(g, sm);
-    g.tot.need(1);
-    const uint32_t big_grid = mg_big_grid(sm);
-    HIP_OK(hipMemsetAsync(g.big.p, 0, 4, s));
-    HIP_OK(hipMemsetAsync(g.tot.p, 0, 8, s));
-    hipEvent_t tev[3] = {nullptr, nullptr, nullptr};
-    if (d->profile) { for (hipEvent_t& ev : tev) HIP_OK(hipEventCreate(&ev)); HIP_OK(hipEventRecord(tev[0], s)); }
-    hipLaunchKernelGGL(k_mgt_select, dim3(std::min<uint32_t>(blocks_for(n * 64), 16384)), dim3(256), 0, s, sm->d_dir, sm->arena.base,
-                       (uint32_t)n, x.items.p, m, min_value, g.thr.p, x.cnt.p, g.big.p, g.tot.p);
-    hipLaunchKernelGGL(k_mgt_select_big, dim3(big_grid), dim3(1024), 0, s, sm->d_dir, sm->arena.base, x.items.p, m, min_value,
-                       g.thr.p, x.cnt.p, g.big.p, g.tot.p);
-    HIP_OK(hipGetLastError());
-    if (d->profile) HIP_OK(hipEventRecord(tev[1], s));
-    x.cnt_tiles = ex_scan_prep(x, s, x.cnt.p, n);
-    if (d->profile) HIP_OK(hipEventRecord(tev[2], s));
-    HIP_OK(hipMemcpyAsync(&seen, g.tot.p, 8, hipMemcpyDeviceToHost, s));
-    kept = ex_read(x.part.p + x.cnt_tiles, s);
-    if (d->profile) {
-      float sel = 0, cnt = 0;
-      HIP_OK(hipEventElapsedTime(&sel, tev[0], tev[1]));
-      HIP_OK(hipEventElapsedTime(&cnt, tev[1], tev[2]));
-      for (hipEvent_t ev : tev) (void)hipEventDestroy(ev);
-      fprintf(stderr, "[smatrix] merge_topk: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
-              sel, cnt, (unsigned long long)kept, seen);
-    }
-    if (kept) {
-      const MgTopk f{g.thr.p, min_value};
-      mg_run_rows(dst, x, g, op, s, n, max_batch, [&](uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
-        HIP_OK(hipMemsetAsync(g.big.p, 0, 4, e));
-        hipLaunchKernelGGL(k_mgt_emit, dim3(std::min<uint32_t>(blocks_for((uint64_t)(r1 - r0) * 64), 16384)), dim3(256), 0, e,
-                           sm->d_dir, sm->arena.base, x.items.p, g.ptr.p, r0, r1, rec, g.big.p, f);
-        hipLaunchKernelGGL(k_mgt_emit_big<true>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                           r0, rec, g.big.p, g.seg_cnt.p, f);
-        hipLaunchKernelGGL(k_mgt_emit_big<false>, dim3(big_grid), dim3(1024), 0, e, sm->d_dir, sm->arena.base, x.items.p, g.ptr.p,
-                           r0, rec, g.big.p, g.seg_cnt.p, f);
-      });
-    }
-  }
-  HIP_OK(hipStreamSynchronize(s));
-  if (n_ops) *n_ops = kept;
-  if (n_dropped) *n_dropped = seen - kept;
-  ex_trim_all(x, false);
-  mg_trim_all(g, false);
-  return 0;
+  if (m == 0) return -1;
+  return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
+    [&](MergeCall& c) {
+      // the selection: every row's threshold and, with it, the number of pairs the row keeps -- the count of an uncut row needs
+      // no pass of its own.  `big` lists the rows of more than GETROW_WAVE_MAX cells here (one word each: it has room for two per
+      // 128 KiB of row tables, and such a row is 128 KiB at least); the emission of every batch starts it afresh.
+      mg_count_filtered(c, true,
+        [&] {
+          c.g.thr.need(c.n);
+          hipLaunchKernelGGL(k_mgt_select, dim3(mg_row_grid(c.n)), dim3(256), 0, c.s, c.sm->d_dir, c.sm->arena.base, (uint32_t)c.n,
+                             c.x.items.p, m, min_value, c.g.thr.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+          hipLaunchKernelGGL(k_mgt_select_big, dim3(c.big_grid), dim3(1024), 0, c.s, c.sm->d_dir, c.sm->arena.base, c.x.items.p, m,
+                             min_value, c.g.thr.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+        },
+        [&](float sel, float cnt) {
+          fprintf(stderr, "[smatrix] merge_topk: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
+                  sel, cnt, (unsigned long long)c.kept, c.seen);
+        });
+    },
+    [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      const MgTopk f{c.g.thr.p, min_value};
+      mg_emit(c, k_mgt_emit, r0, r1, rec, e, f);
+      mg_emit_big(c, k_mgt_emit_big<true>, r0, rec, e, f);
+      mg_emit_big(c, k_mgt_emit_big<false>, r0, rec, e, f);
+    });
 }
 
 int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows, const uint64_t* d_row_ptr,

@@ -37,20 +37,23 @@ def _merge_op(op):
     raise ValueError("op must be 'set', 'incr' or 'decr', not %r" % (op,))
 
 
+def _check_u32(name, val, lo=0):
+    if not isinstance(val, (int, np.integer)) or isinstance(val, bool) or not lo <= val <= 0xFFFFFFFF:
+        raise ValueError("%s must be an integer in %d .. 2**32 - 1, not %r" % (name, lo, val))
+
+
 def _scale_args(num, den, min_value):
     """merge_scaled's num / den / min_value: uint32 each, 1 <= num <= den; anything else is a ValueError"""
     for name, val in (("num", num), ("den", den), ("min_value", min_value)):
-        if not isinstance(val, (int, np.integer)) or isinstance(val, bool) or not 0 <= val <= 0xFFFFFFFF:
-            raise ValueError("%s must be an integer in 0 .. 2**32 - 1, not %r" % (name, val))
+        _check_u32(name, val)
     if not 1 <= num <= den:
         raise ValueError("1 <= num <= den is required, not %r / %r" % (num, den))
 
 
 def _topk_args(m, min_value):
     """merge_topk's m / min_value: uint32 each, m >= 1; anything else is a ValueError"""
-    for name, val, lo in (("m", m, 1), ("min_value", min_value, 0)):
-        if not isinstance(val, (int, np.integer)) or isinstance(val, bool) or not lo <= val <= 0xFFFFFFFF:
-            raise ValueError("%s must be an integer in %d .. 2**32 - 1, not %r" % (name, lo, val))
+    _check_u32("m", m, 1)
+    _check_u32("min_value", min_value)
 
 
 def _sessions(sessions):
@@ -329,70 +332,60 @@ class SparseMatrix:
         return torch.sparse_coo_tensor(torch.stack([x, y]), v, size=tuple(size), is_coalesced=True)
 
     # ---- merge of two matrices, CSR import (include/smatrix_batch.h smatrix_merge / smatrix_import_csr) ----
+    def _merge_call(self, name, other, op, *args, check=None, max_batch=0):
+        """smatrix_<name>(self, other, op, *args, max_batch, &n_ops[, &n_dropped]) behind the checks, none of which touches a
+        handle: the op, the flavour's own arguments (check), other's type.  check given: the flavour drops pairs, and
+        -> (ops applied, pairs dropped); else -> ops applied."""
+        o = _merge_op(op)
+        if check:
+            check(*args)
+        if not isinstance(other, SparseMatrix):
+            raise TypeError("%s needs another SparseMatrix, not %r" % (name, type(other).__name__))
+        out = [C.c_uint64(0) for _ in range(2 if check else 1)]
+        if getattr(self._lib, "smatrix_" + name)(self._h, other._h, o, *map(int, args), int(max_batch), *map(C.byref, out)) != 0:
+            raise ValueError("smatrix_%s refused: a matrix cannot be merged into itself, and both must be on one device" % name)
+        return tuple(v.value for v in out) if check else out[0].value
+
+    def _copy_by(self, method, filename, *args):
+        """a NEW matrix (filename: see SparseMatrix) filled by method(new, self, *args); closed again if that raises"""
+        m = SparseMatrix(filename)
+        try:
+            method(m, self, *args)
+        except Exception:
+            m.close()
+            raise
+        return m
+
     def merge(self, other, op="incr", max_batch=0):
         """self[x, y] op= other[x, y] for every pair of other, on the GPU in internal batches of at most
         max(max_batch, other's longest row) ops (0: 2**24): -> the number of ops applied.  other is not modified."""
-        o = _merge_op(op)
-        if not isinstance(other, SparseMatrix):
-            raise TypeError("merge needs another SparseMatrix, not %r" % (type(other).__name__,))
-        n = C.c_uint64(0)
-        if self._lib.smatrix_merge(self._h, other._h, o, int(max_batch), C.byref(n)) != 0:
-            raise ValueError("smatrix_merge refused: a matrix cannot be merged into itself, and both must be on one device")
-        return n.value
+        return self._merge_call("merge", other, op, max_batch=max_batch)
 
     def merge_scaled(self, other, op="incr", num=1, den=1, min_value=0, max_batch=0):
         """merge with a decay and a filter: every pair (y, v) of other becomes v' = v * num // den and is dropped when
         v' < min_value (or when it would be the empty cell (0, 0)); the others are applied as self[x, y] op= v'.
         1 <= num <= den <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified."""
-        o = _merge_op(op)
-        _scale_args(num, den, min_value)
-        if not isinstance(other, SparseMatrix):
-            raise TypeError("merge_scaled needs another SparseMatrix, not %r" % (type(other).__name__,))
-        n, dropped = C.c_uint64(0), C.c_uint64(0)
-        if self._lib.smatrix_merge_scaled(self._h, other._h, o, int(num), int(den), int(min_value), int(max_batch),
-                                          C.byref(n), C.byref(dropped)) != 0:
-            raise ValueError("smatrix_merge_scaled refused: a matrix cannot be merged into itself, and both must be on one device")
-        return n.value, dropped.value
+        return self._merge_call("merge_scaled", other, op, num, den, min_value, check=_scale_args, max_batch=max_batch)
 
     def pruned(self, min_value=1, num=1, den=1, filename=None):
         """a NEW matrix (in memory, or file-backed when filename is given) that holds self's pairs scaled by num / den, without
         those below min_value: no dead cells, row tables as small as the survivors allow -- the end of a sliding-window cycle
         (total += today; total -= day_30; total = total.pruned()).  self is not modified."""
         _scale_args(num, den, min_value)
-        m = SparseMatrix(filename)
-        try:
-            m.merge_scaled(self, "set", num, den, min_value)
-        except Exception:
-            m.close()
-            raise
-        return m
+        return self._copy_by(SparseMatrix.merge_scaled, filename, "set", num, den, min_value)
 
     def merge_topk(self, other, m, op="set", min_value=1, max_batch=0):
         """merge that keeps the m heaviest pairs of every row of other: of the pairs (y != 0, v >= min_value) those of the largest
         v, equal values by ascending column; the column-0 pair (the CF total) is kept beside them when v >= min_value.  The kept
         pairs are applied as self[x, y] op= v.  1 <= m <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified."""
-        o = _merge_op(op)
-        _topk_args(m, min_value)
-        if not isinstance(other, SparseMatrix):
-            raise TypeError("merge_topk needs another SparseMatrix, not %r" % (type(other).__name__,))
-        n, dropped = C.c_uint64(0), C.c_uint64(0)
-        if self._lib.smatrix_merge_topk(self._h, other._h, o, int(m), int(min_value), int(max_batch),
-                                        C.byref(n), C.byref(dropped)) != 0:
-            raise ValueError("smatrix_merge_topk refused: a matrix cannot be merged into itself, and both must be on one device")
-        return n.value, dropped.value
+        return self._merge_call("merge_topk", other, op, m, min_value, check=_topk_args, max_batch=max_batch)
 
     def truncated(self, m, min_value=1, filename=None):
         """a NEW matrix (in memory, or file-backed when filename is given) that holds, of every row of self, the m heaviest pairs
         of at least min_value and the column-0 pair: at most m + 1 pairs per row, the serving copy of an item-kNN recommender
         (total += today; total -= day_30; serving = total.truncated(m)).  self is not modified."""
         _topk_args(m, min_value)
-        m_new = SparseMatrix(filename)
-        try:
-            m_new.merge_topk(self, m, "set", min_value)
-        except Exception:
-            m_new.close()
-            raise
-        return m_new
+        return self._copy_by(SparseMatrix.merge_topk, filename, m, "set", min_value)
 
     def __iadd__(self, other):
         if not isinstance(other, SparseMatrix):

@@ -16,76 +16,10 @@ import numpy as np
 import pytest
 
 from libsmatrix_amd import SparseMatrix
-from libsmatrix_amd.stream import Stream
+from tests.merge_helpers import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, col0_rows, device, ops_of,  # noqa: F401
+                                 src_dense, src_one_long_row, src_quirks, src_zipf)
 
 pytestmark = pytest.mark.gpu
-
-GET, SET, INCR, DECR = 0, 1, 2, 3
-OPS = {"set": SET, "incr": INCR, "decr": DECR}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def device():
-    import libsmatrix_amd
-    assert libsmatrix_amd.device_available(), "no HIP device: the product has no CPU fallback"
-
-
-def nonempty(kv):
-    return kv[(kv[:, 0] != 0) | (kv[:, 1] != 0)]
-
-
-def ops_of(o):
-    """the ops a merge of this oracle's matrix applies: rows in list_rows() order, non-empty slots in slot order"""
-    xs, ys, vs = [], [], []
-    for x in o.list_rows().tolist():
-        ne = nonempty(o.row_slots(x))
-        xs.append(np.full(ne.shape[0], x, np.uint32)); ys.append(ne[:, 0]); vs.append(ne[:, 1])
-    if not xs:
-        z = np.zeros(0, np.uint32)
-        return z, z, z
-    return np.concatenate(xs), np.concatenate(ys).astype(np.uint32), np.concatenate(vs).astype(np.uint32)
-
-
-def col0_rows(*oracles):
-    out = set()
-    for o in oracles:
-        x, y, _ = ops_of(o)
-        out |= set(x[y == 0].tolist())
-    return out
-
-
-def probe_invariant(slots, x):
-    size = slots.shape[0]
-    occupied = (slots[:, 0] != 0) | (slots[:, 1] != 0)
-    keys = slots[occupied, 0]
-    assert np.unique(keys).size == keys.size, ("a key twice in row", x)
-    for i in np.flatnonzero(occupied).tolist():
-        p = int(slots[i, 0]) % size
-        while p != i:
-            assert occupied[p], ("an empty slot before key %d of row %d" % (slots[i, 0], x))
-            p = (p + 1) % size
-
-
-def check(m, o, sides, col0, tag):
-    """m against o for every row / cell of the oracles in `sides` (o itself included)"""
-    ids, cx, cy = set(), [], []
-    for s in sides:
-        ids |= set(s.list_rows().tolist())
-        x, y, _ = ops_of(s)
-        cx.append(x); cy.append(y)
-    for x in sorted(ids):
-        mi, oi = m.row_info(x), o.row_info(x)
-        assert (mi is None) == (oi is None), (tag, "row set", x, mi, oi)
-        if oi is None:
-            continue
-        if x not in col0:
-            assert mi == oi, (tag, "size / used of row", x, mi, oi)
-        else:
-            probe_invariant(m.row_slots(x), x)
-    cx, cy = np.concatenate(cx), np.concatenate(cy)
-    got, want = m.get_batch(cx, cy), o.apply(GET, cx, cy)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (tag, bad.size, [(int(cx[i]), int(cy[i]), int(got[i]), int(want[i])) for i in bad[:8]])
 
 
 def merged(dst, o_dst, src, o_src, op, max_batch=0, tag=""):
@@ -99,53 +33,13 @@ def merged(dst, o_dst, src, o_src, op, max_batch=0, tag=""):
     return n
 
 
-def both(m, o, op, x, y, v):
-    m.apply_batch(op, x, y, v, results=False)
-    o.apply(op, x, y, v)
-
-
-def assert_export_equal(a, b, tag=""):
-    for k, (u, v) in enumerate(zip(a, b)):
-        assert u.shape == v.shape, (tag, k, u.shape, v.shape)
-        assert (u == v).all(), (tag, k)
-
-
 def without_empty_rows(ex):
     rows, ptr, pairs = ex
     keep = np.diff(ptr.astype(np.int64)) > 0
     return rows[keep], np.concatenate([ptr[:1], ptr[1:][keep]]), pairs
 
 
-# ---- the sources of case 1 -------------------------------------------------------------------------------------------------
-def src_quirks(m, o, golden):
-    for op, args, _ in golden("quirks")["transcript"]:
-        if op in ("set", "incr", "decr"):
-            assert getattr(m, op)(*args) == getattr(o, op)(*args), (op, args)
-
-
-def src_zipf(m, o, golden):
-    x, y = Stream("zipf", 12345, 1000000, 1.1, 1).fill(0, 1000000)
-    for k in range(5):
-        s = slice(k * 200000, (k + 1) * 200000)
-        both(m, o, INCR, x[s], y[s], np.ones(200000, np.uint32))
-
-
-def src_dense(m, o, golden):
-    x, y = Stream("zipf", 77, 300000, 1.1, 0).fill(0, 800000)
-    x = (x % 40).astype(np.uint32)                                      # few rows -> large tables of dense (unscrambled) keys
-    for k in range(4):
-        s = slice(k * 200000, (k + 1) * 200000)
-        both(m, o, INCR, x[s], y[s], ((x[s] + y[s]) % 3 + 1).astype(np.uint32))
-
-
-def src_one_long_row(m, o, golden):
-    rng = np.random.default_rng(5)
-    ys = (rng.permutation(1 << 20)[:200000] + 1).astype(np.uint32)
-    both(m, o, SET, np.full(ys.size, 7, np.uint32), ys, rng.integers(1, 1 << 32, ys.size, dtype=np.uint32))
-    xs = np.repeat(np.arange(100000, 110000, dtype=np.uint32), 8)
-    both(m, o, INCR, xs, rng.integers(1, 1 << 32, xs.size, dtype=np.uint32), rng.integers(1, 9, xs.size, dtype=np.uint32))
-
-
+# ---- case 1 ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("source", [src_quirks, src_zipf, src_dense, src_one_long_row])
 def test_merge_into_an_empty_matrix_reproduces_the_source(oracle_mod, golden, source):
     src, o_src = SparseMatrix(), oracle_mod.Oracle()

@@ -10,40 +10,18 @@ every cell of the union; for rows that hold no column-0 pair on either side, siz
 probe invariant (their `used` depends on the history in the reference itself, Q1/Q2).  All comparisons are exact.  The cases keep
 column-0 values from returning to a STORED 0 (Q3): a source's (0, 1) cell that a decay takes to 0 is dropped, never stored."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from libsmatrix_amd import SparseMatrix
-from libsmatrix_amd.stream import Stream
+from tests import merge_helpers as H
+from tests.merge_helpers import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, col0_rows, device, ops_of, u32)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GET, SET, INCR, DECR = 0, 1, 2, 3
-OPS = {"set": SET, "incr": INCR, "decr": DECR}
 PARAMS = [(1, 1, 1), (1, 2, 0), (1, 2, 1), (9, 10, 2), (1, 3, 1)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def device():
-    import libsmatrix_amd
-    assert libsmatrix_amd.device_available(), "no HIP device: the product has no CPU fallback"
-
-
-def nonempty(kv):
-    return kv[(kv[:, 0] != 0) | (kv[:, 1] != 0)]
-
-
-def ops_of(o):
-    """the candidates of a merge of this oracle's matrix: rows in list_rows() order, non-empty slots in slot order"""
-    xs, ys, vs = [], [], []
-    for x in o.list_rows().tolist():
-        ne = nonempty(o.row_slots(x))
-        xs.append(np.full(ne.shape[0], x, np.uint32)); ys.append(ne[:, 0]); vs.append(ne[:, 1])
-    if not xs:
-        z = np.zeros(0, np.uint32)
-        return z, z, z
-    return np.concatenate(xs), np.concatenate(ys).astype(np.uint32), np.concatenate(vs).astype(np.uint32)
 
 
 def scaled(cand, num, den, min_value):
@@ -52,47 +30,6 @@ def scaled(cand, num, den, min_value):
     w = (v.astype(np.uint64) * np.uint64(num) // np.uint64(den)).astype(np.uint32)
     keep = (w >= np.uint32(min_value)) & ((y != 0) | (w != 0))
     return (x[keep], y[keep], w[keep]), int(x.size - np.count_nonzero(keep))
-
-
-def col0_rows(*cands):
-    out = set()
-    for x, y, _ in cands:
-        out |= set(x[y == 0].tolist())
-    return out
-
-
-def probe_invariant(slots, x):
-    size = slots.shape[0]
-    occupied = (slots[:, 0] != 0) | (slots[:, 1] != 0)
-    keys = slots[occupied, 0]
-    assert np.unique(keys).size == keys.size, ("a key twice in row", x)
-    for i in np.flatnonzero(occupied).tolist():
-        p = int(slots[i, 0]) % size
-        while p != i:
-            assert occupied[p], ("an empty slot before key %d of row %d" % (slots[i, 0], x))
-            p = (p + 1) % size
-
-
-def check(m, o, cands, col0, tag):
-    """m against o for every row / cell of the candidate lists in `cands` and of o itself"""
-    cands = list(cands) + [ops_of(o)]
-    ids = set(o.list_rows().tolist())
-    for x, _, _ in cands:
-        ids |= set(np.unique(x).tolist())
-    col0 = col0 | col0_rows(*cands)
-    for x in sorted(ids):
-        mi, oi = m.row_info(x), o.row_info(x)
-        assert (mi is None) == (oi is None), (tag, "row set", x, mi, oi)
-        if oi is None:
-            continue
-        if x not in col0:
-            assert mi == oi, (tag, "size / used of row", x, mi, oi)
-        else:
-            probe_invariant(m.row_slots(x), x)
-    cx, cy = np.concatenate([c[0] for c in cands]), np.concatenate([c[1] for c in cands])
-    got, want = m.get_batch(cx, cy), o.apply(GET, cx, cy)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (tag, bad.size, [(int(cx[i]), int(cy[i]), int(got[i]), int(want[i])) for i in bad[:8]])
 
 
 def merged_scaled(dst, o_dst, src, cand, op, num, den, min_value, max_batch=0, tag=""):
@@ -105,21 +42,6 @@ def merged_scaled(dst, o_dst, src, cand, op, num, den, min_value, max_batch=0, t
     assert (n, d) == (ops[0].size, dropped), (tag, (n, d), (ops[0].size, dropped))
     check(dst, o_dst, (before, cand), set(), tag)
     return n, d
-
-
-def both(m, o, op, x, y, v):
-    m.apply_batch(op, x, y, v, results=False)
-    o.apply(op, x, y, v)
-
-
-def assert_export_equal(a, b, tag=""):
-    for k, (u, v) in enumerate(zip(a, b)):
-        assert u.shape == v.shape, (tag, k, u.shape, v.shape)
-        assert (u == v).all(), (tag, k)
-
-
-def u32(*a):
-    return np.array(a, np.uint32)
 
 
 # ---- the sources of case 1 -------------------------------------------------------------------------------------------------
@@ -141,44 +63,11 @@ def additions(m, o):
     both(m, o, DECR, np.full(2995, 3000400, np.uint32), ys[5:], np.full(2995, 2, np.uint32))
 
 
-def src_quirks(m, o, golden):
-    for op, args, _ in golden("quirks")["transcript"]:
-        if op in ("set", "incr", "decr"):
-            assert getattr(m, op)(*args) == getattr(o, op)(*args), (op, args)
-    additions(m, o)
-
-
-def src_zipf(m, o, golden):
-    x, y = Stream("zipf", 12345, 1000000, 1.1, 1).fill(0, 300000)
-    for k in range(3):
-        s = slice(k * 100000, (k + 1) * 100000)
-        both(m, o, INCR, x[s], y[s], np.ones(100000, np.uint32))
-    additions(m, o)
-
-
-def src_dense(m, o, golden):
-    x, y = Stream("zipf", 77, 300000, 1.1, 0).fill(0, 400000)
-    x = (x % 40).astype(np.uint32)                                      # few rows -> large tables of dense (unscrambled) keys
-    for k in range(2):
-        s = slice(k * 200000, (k + 1) * 200000)
-        both(m, o, INCR, x[s], y[s], ((x[s] + y[s]) % 3 + 1).astype(np.uint32))
-    additions(m, o)
-
-
-def src_one_long_row(m, o, golden):
-    """row 7: 200000 keys -> a table of 2^19 cells, 16 segments; values 0 (dead), 1, 2, 3 and large ones, mixed in every segment"""
-    rng = np.random.default_rng(5)
-    ys = (rng.permutation(1 << 20)[:200000] + 1).astype(np.uint32)
-    vs = rng.integers(1, 1 << 32, ys.size, dtype=np.uint32)
-    small = rng.integers(0, 8, ys.size)
-    vs = np.where(small < 4, small, vs).astype(np.uint32)               # half of them 0, 1, 2 or 3
-    both(m, o, INCR, np.full(ys.size, 7, np.uint32), ys, vs)            # (an incr by 0 creates the cell)
-    xs = np.repeat(np.arange(100000, 110000, dtype=np.uint32), 8)
-    both(m, o, INCR, xs, rng.integers(1, 1 << 32, xs.size, dtype=np.uint32), rng.integers(1, 9, xs.size, dtype=np.uint32))
-    additions(m, o)
-
-
-SOURCES = {f.__name__: f for f in (src_quirks, src_zipf, src_dense, src_one_long_row)}
+# (sizes: a third to a half of tests/test_gpu_merge.py's; the long row with small and dead values mixed into every segment)
+SOURCES = {"src_quirks": functools.partial(H.src_quirks, additions=additions),
+           "src_zipf": functools.partial(H.src_zipf, n=300000, chunk=100000, additions=additions),
+           "src_dense": functools.partial(H.src_dense, n=400000, additions=additions),
+           "src_one_long_row": functools.partial(H.src_one_long_row, small=True, additions=additions)}
 
 
 @pytest.fixture(scope="module")
@@ -249,7 +138,7 @@ def overlapping(oracle_mod):
 
 def state(m, o):
     ids = sorted(set(o.list_rows().tolist()))
-    col0 = col0_rows(ops_of(o))
+    col0 = col0_rows(o)
     return m.export("sorted"), [m.row_info(x) for x in ids if x not in col0]
 
 

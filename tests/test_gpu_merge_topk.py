@@ -1,5 +1,5 @@
 """GPU (-m gpu): smatrix_merge_topk (include/smatrix_batch.h; SparseMatrix.merge_topk, SparseMatrix.truncated).  Every case runs
-next to oracle_mod.Oracle(), in the manner of tests/test_gpu_merge_scaled.py, whose ops_of / check / probe_invariant are used.
+next to oracle_mod.Oracle(), in the manner of tests/test_gpu_merge_scaled.py, on the helpers of tests/merge_helpers.py.
 
 Expected ops, from numpy alone: the source oracle's candidates (rows in list_rows() order, non-empty slots in slot order); per row
 the eligible pairs (y != 0, v >= min_value) sorted by (-v, y), the first m of them kept; the head pair (y == 0) kept iff
@@ -13,17 +13,11 @@ import numpy as np
 import pytest
 
 from libsmatrix_amd import SparseMatrix
-from tests.test_gpu_merge_scaled import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, ops_of, u32)
+from tests.merge_helpers import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, device, ops_of, u32)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 M_MAX = 0xFFFFFFFF
-
-
-@pytest.fixture(scope="module", autouse=True)
-def device():
-    import libsmatrix_amd
-    assert libsmatrix_amd.device_available(), "no HIP device: the product has no CPU fallback"
 
 
 def topk(cand, m, min_value):

@@ -1,29 +1,14 @@
 """CPU: smatrix_merge / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h) are declared in the header, exported
 by the library, bound by the ctypes layer with the declared argument counts, and reachable from SparseMatrix.  No compute calls."""
-import os
-import re
-import subprocess
+import operator
 
+import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "libsmatrix_amd", "lib")
+from tests.merge_abi_helpers import (BAD_OPS, assert_binding_matches_the_header, assert_methods, assert_raises, built,  # noqa: F401
+                                     declared_args, exported, in_the_shim)
+
 CALLS = {"smatrix_merge": 5, "smatrix_import_csr": 8, "smatrix_import_csr_dev": 9}
-
-
-@pytest.fixture(scope="module")
-def built():
-    if not os.path.exists(os.path.join(LIBDIR, "smatrix.so")):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "libsmatrix_amd", "csrc")], check=True)
-    return LIBDIR
-
-
-def declared_args(name):
-    src = open(os.path.join(ROOT, "include", "smatrix_batch.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, "%s is not declared in include/smatrix_batch.h" % name
-    return [a.strip() for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(CALLS))
@@ -32,52 +17,30 @@ def test_merge_prototypes_are_in_the_header(name):
 
 
 def test_merge_symbols_are_exported(built):
-    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(built, "smatrix.so")], check=True,
-                         capture_output=True, text=True).stdout
-    syms = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert set(CALLS) <= syms
+    assert set(CALLS) <= exported(built)
 
 
 def test_the_shim_still_carries_the_reference_symbols_only(built):
-    out = subprocess.run(["nm", "--defined-only", os.path.join(built, "smatrix.o")], check=True, capture_output=True, text=True).stdout
-    syms = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
-    assert not (set(CALLS) & syms)
+    assert not (set(CALLS) & in_the_shim(built))
 
 
 @pytest.mark.parametrize("name", sorted(CALLS))
 def test_merge_binding_matches_the_header(built, name):
-    from libsmatrix_amd import _lib
-    lib = _lib.load()
-    fn = getattr(lib, name)
-    assert len(fn.argtypes) == len(declared_args(name)) == CALLS[name]
+    assert_binding_matches_the_header(name, CALLS[name])
 
 
 def test_sparse_matrix_has_the_merge_methods():
-    from libsmatrix_amd import SparseMatrix
-    for meth in ("merge", "__iadd__", "__isub__", "import_csr", "import_csr_dev", "from_sparse_coo"):
-        assert callable(getattr(SparseMatrix, meth, None)), meth
+    assert_methods("merge", "__iadd__", "__isub__", "import_csr", "import_csr_dev", "from_sparse_coo")
 
 
-@pytest.mark.parametrize("op", ["get", "add", "", None, 0, 4, True])
+@pytest.mark.parametrize("op", BAD_OPS)
 def test_unknown_op_is_refused_before_any_device_call(op):
-    import numpy as np
-    from libsmatrix_amd import SparseMatrix
-    a = SparseMatrix.__new__(SparseMatrix)          # no handles: the op is checked first
-    b = SparseMatrix.__new__(SparseMatrix)
-    with pytest.raises(ValueError):
-        a.merge(b, op)
-    with pytest.raises(ValueError):
-        a.import_csr(np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros((0, 2), np.uint32), op)
-    with pytest.raises(ValueError):
-        a.import_csr_dev(0, 0, 0, op, n_rows=0)
-    with pytest.raises(ValueError):
-        a.from_sparse_coo(None, op)
+    assert_raises(ValueError,
+                  lambda a, b: a.merge(b, op),
+                  lambda a, b: a.import_csr(np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros((0, 2), np.uint32), op),
+                  lambda a, b: a.import_csr_dev(0, 0, 0, op, n_rows=0),
+                  lambda a, b: a.from_sparse_coo(None, op))
 
 
 def test_iadd_of_something_else_is_a_type_error():
-    from libsmatrix_amd import SparseMatrix
-    a = SparseMatrix.__new__(SparseMatrix)
-    with pytest.raises(TypeError):
-        a += 3
-    with pytest.raises(TypeError):
-        a.merge([1, 2, 3])
+    assert_raises(TypeError, lambda a, b: operator.iadd(a, 3), lambda a, b: a.merge([1, 2, 3]))

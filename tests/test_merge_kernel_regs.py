@@ -1,36 +1,64 @@
-"""The record-emission kernels of smatrix_merge / smatrix_import_csr (kernels/merge.hpp) keep their register budget (no GPU
-needed: the counts are read from the gfx950 code object in smatrix.so).
+"""The kernels of the merge family and of the CSR import (kernels/merge.hpp: k_mg_* of smatrix_merge / smatrix_import_csr, k_mgx_* of
+smatrix_merge_scaled, k_mgt_* of smatrix_merge_topk) keep their register budget (no GPU needed: the counts are read from the gfx950
+code object in smatrix.so).
 
-k_mg_emit streams row tables like k_getrow and hides the latency of its loads the same way, by residency: its bound is k_getrow's
-(tests/test_kernel_regs.py: 56 VGPRs -> 8 waves per SIMD, the most a CDNA SIMD holds; the granule is 8 registers, 512 per SIMD),
-so its occupancy is never lower.  The segment kernels run 1024-lane workgroups: two of them per CU need <= 64.  None of them may
-use scratch memory."""
+The wave-per-row kernels stream row tables like k_getrow and hide the latency of their loads the same way, by residency: their
+bound is k_getrow's (tests/test_kernel_regs.py: 56 VGPRs -> 8 waves per SIMD, the most a CDNA SIMD holds; the granule is 8
+registers, 512 per SIMD), so their occupancy is never lower.  The segment kernels run 1024-lane workgroups: two of them per CU need
+<= 64.  None of them may spill or use scratch memory.  Into that have to fit the scaled merge's transform (a 32 x 32 -> 64 bit
+product, an FP64 estimate of the quotient and its correction) and the top-k selection (a 64-bit rank key, a radix pass with ballots
+and LDS adds, the walk over the 256 bins), SGPRs included: the 1024-lane selection walks the bins without the shuffle scan's lane
+tests for that reason."""
 import os, re, subprocess, sys
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "libsmatrix_amd", "lib", "smatrix.so")
 
 # kernel (demangled, as tools/kernel_regs.py prints it) -> max VGPRs
-BOUNDS = {
+MERGE = {
     "smx::k_mg_emit": 56,
     "smx::k_mg_emit_big<true>": 64,
     "smx::k_mg_emit_big<false>": 64,
     "smx::k_mg_emit_csr": 56,
 }
+SCALED = {
+    "smx::k_mgx_count": 56,
+    "smx::k_mgx_emit": 56,
+    "smx::k_mgx_count_big": 64,
+    "smx::k_mgx_emit_big": 64,
+}
+TOPK = {
+    "smx::k_mgt_select": 56,
+    "smx::k_mgt_emit": 56,
+    "smx::k_mgt_select_big": 64,
+    "smx::k_mgt_emit_big<true>": 64,
+    "smx::k_mgt_emit_big<false>": 64,
+}
 
 
-def test_emit_kernels_keep_their_registers_and_use_no_scratch():
+def check(bounds, flt):
     if not os.path.exists(LIB):
         subprocess.run(["make", "-C", os.path.join(ROOT, "libsmatrix_amd", "csrc")], check=True)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), LIB, "k_mg_"], capture_output=True, text=True, timeout=600).stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), LIB, flt], capture_output=True, text=True, timeout=600).stdout
     seen = {}
     for line in out.splitlines():
         m = re.match(r"(?:void )?(\S.*?)\s+sgpr\s+(\d+) \(spilled\s+(\d+)\)\s+vgpr\s+(\d+) \(spilled (\d+)\)\s+lds \d+\s+scratch (\d+)", line)
         if m:
             seen[m.group(1).strip()] = (int(m.group(4)), int(m.group(3)) + int(m.group(5)), int(m.group(6)))
-    for name, max_v in BOUNDS.items():
+    for name, max_v in bounds.items():
         assert name in seen, "kernel %s is not in the library:\n%s" % (name, out[:500])
         v, spilled, scratch = seen[name]
         assert v <= max_v, "%s: %d VGPRs, the bound is %d" % (name, v, max_v)
         assert spilled == 0 and scratch == 0, "%s: %d spilled registers, %d bytes of scratch" % (name, spilled, scratch)
+
+
+def test_emit_kernels_keep_their_registers_and_use_no_scratch():
+    check(MERGE, "k_mg_")
+
+
+def test_scaled_merge_kernels_keep_their_registers_and_use_no_scratch():
+    check(SCALED, "k_mgx_")
+
+
+def test_topk_merge_kernels_keep_their_registers_and_use_no_scratch():
+    check(TOPK, "k_mgt_")

@@ -1,95 +1,51 @@
 """CPU: smatrix_merge_scaled (include/smatrix_batch.h) is declared in the header with its 9 arguments, exported by the library
 and not by the shim, bound by the ctypes layer with the declared argument count, and reachable from SparseMatrix as merge_scaled
 and pruned, whose argument checks fire before any handle is touched.  No compute calls."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBDIR = os.path.join(ROOT, "libsmatrix_amd", "lib")
+from tests.merge_abi_helpers import (BAD_MIN_VALUES, BAD_OPS, assert_binding_matches_the_header, assert_methods, assert_raises,  # noqa: F401
+                                     built, declared_args, exported, in_the_shim)
+
 NAME, NARGS = "smatrix_merge_scaled", 9
 
 
-@pytest.fixture(scope="module")
-def built():
-    if not os.path.exists(os.path.join(LIBDIR, "smatrix.so")):
-        subprocess.run(["make", "-C", os.path.join(ROOT, "libsmatrix_amd", "csrc")], check=True)
-    return LIBDIR
-
-
-def declared_args():
-    src = open(os.path.join(ROOT, "include", "smatrix_batch.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % NAME, src)
-    assert m, "%s is not declared in include/smatrix_batch.h" % NAME
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 def test_the_prototype_is_in_the_header():
-    args = declared_args()
+    args = declared_args(NAME)
     assert len(args) == NARGS, args
     assert [a.split()[-1].lstrip("*") for a in args] == ["dst", "src", "op", "num", "den", "min_value", "max_batch", "n_ops", "n_dropped"]
 
 
 def test_the_symbol_is_exported(built):
-    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(built, "smatrix.so")], check=True,
-                         capture_output=True, text=True).stdout
-    assert NAME in {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert NAME in exported(built)
 
 
 def test_the_shim_still_carries_the_reference_symbols_only(built):
-    out = subprocess.run(["nm", "--defined-only", os.path.join(built, "smatrix.o")], check=True, capture_output=True, text=True).stdout
-    assert NAME not in {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    assert NAME not in in_the_shim(built)
 
 
 def test_the_binding_matches_the_header(built):
-    from libsmatrix_amd import _lib
-    fn = getattr(_lib.load(), NAME)
-    assert len(fn.argtypes) == len(declared_args()) == NARGS
+    assert_binding_matches_the_header(NAME, NARGS)
 
 
 def test_sparse_matrix_has_the_methods():
-    from libsmatrix_amd import SparseMatrix
-    for meth in ("merge_scaled", "pruned"):
-        assert callable(getattr(SparseMatrix, meth, None)), meth
+    assert_methods("merge_scaled", "pruned")
 
 
-def handleless():
-    from libsmatrix_amd import SparseMatrix
-    return SparseMatrix.__new__(SparseMatrix), SparseMatrix.__new__(SparseMatrix)      # no handles: the arguments are checked first
-
-
-@pytest.mark.parametrize("op", ["get", "add", "", None, 0, 4, True])
+@pytest.mark.parametrize("op", BAD_OPS)
 def test_unknown_op_is_refused_before_any_device_call(op):
-    a, b = handleless()
-    with pytest.raises(ValueError):
-        a.merge_scaled(b, op)
+    assert_raises(ValueError, lambda a, b: a.merge_scaled(b, op))
 
 
 @pytest.mark.parametrize("num, den", [(0, 1), (1, 0), (0, 0), (2, 1), (10, 9), (1, 1 << 32), (1 << 32, 1 << 32), (-1, 2), (1, -2),
                                       (0.5, 1), (1, 2.0), (None, 1), ("1", "2"), (True, True)])
 def test_bad_fraction_is_refused_before_any_device_call(num, den):
-    a, b = handleless()
-    with pytest.raises(ValueError):
-        a.merge_scaled(b, "incr", num, den)
-    with pytest.raises(ValueError):
-        a.pruned(1, num, den)
+    assert_raises(ValueError, lambda a, b: a.merge_scaled(b, "incr", num, den), lambda a, b: a.pruned(1, num, den))
 
 
-@pytest.mark.parametrize("min_value", [-1, 1 << 32, 1.5, None])
+@pytest.mark.parametrize("min_value", BAD_MIN_VALUES)
 def test_bad_min_value_is_refused_before_any_device_call(min_value):
-    a, b = handleless()
-    with pytest.raises(ValueError):
-        a.merge_scaled(b, "set", 1, 2, min_value)
-    with pytest.raises(ValueError):
-        a.pruned(min_value)
+    assert_raises(ValueError, lambda a, b: a.merge_scaled(b, "set", 1, 2, min_value), lambda a, b: a.pruned(min_value))
 
 
 def test_something_else_than_a_matrix_is_a_type_error():
-    a, _ = handleless()
-    with pytest.raises(TypeError):
-        a.merge_scaled([1, 2, 3])
-    with pytest.raises(TypeError):
-        a.merge_scaled(3, "set", 1, 2, 1)
+    assert_raises(TypeError, lambda a, b: a.merge_scaled([1, 2, 3]), lambda a, b: a.merge_scaled(3, "set", 1, 2, 1))
