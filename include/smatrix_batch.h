@@ -252,6 +252,33 @@ int smatrix_merge_scaled(smatrix_t* dst, smatrix_t* src, int op, uint32_t num, u
  *   close the old one).  Runs on dst's own stream and returns when done. */
 int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint32_t min_value, uint64_t max_batch,
                        uint64_t* n_ops, uint64_t* n_dropped);
+
+/* smatrix_merge_topk_by: smatrix_merge_topk with the rank of a row's pairs chosen by the caller.  Everything not said here is
+ *   smatrix_merge_topk's contract, word for word: candidates, head pair, eligibility, the op applied -- op(x, y, v) with the RAW
+ *   v, so the copy scores its kept pairs as src does --, the counts, the batch contract, bounded scratch, locks, mirrors, files,
+ *   the one checkpoint, src untouched.
+ * rank == SMATRIX_RANK_VALUE:  smatrix_merge_topk itself (the same code path).
+ * rank == SMATRIX_RANK_COSINE: the row keeps the pairs that SCORE best in the CF read path (smatrix_cf_neighbors, _topk,
+ *   _recommend), not the heaviest ones: a popular item co-occurs with everything, has a large v and a small cosine, and under
+ *   the value rank crowds an item's truly similar neighbours out of the kept m.
+ *   total(i) = what smatrix_get(src, i, 0) returns once the mirror is written back; 0 without a row or a head pair.
+ *   The score of the pair (y, v) of row x, in IEEE double, expression for expression that of smatrix_cf_neighbors:
+ *       tb = total(y); if (tb == 0) tb = 1;
+ *       den = sqrt((double)total(x)) * sqrt((double)tb);
+ *       score = (den != 0.0 && !((double)v > den)) ? (double)v / den : 0.0;
+ *   Rank key: the pair (bit pattern of score as uint64, 0xFFFFFFFF - y), compared lexicographically, larger is better: by
+ *       score (scores are >= 0, so their bit patterns order as the doubles do), equal scores by ascending column.  Keys are
+ *       unique within a row; the row keeps its min(m, eligible) eligible pairs of the largest keys.
+ *   A row without a head pair scores 0 everywhere and keeps its m LOWEST eligible columns.  A dead cell (v == 0, eligible with
+ *       min_value == 0) scores 0, as does a pair with v > den.
+ *   The kept set depends on src's contents alone -- not on slot order, insertion history or max_batch.
+ * Device memory beyond the matrices: smatrix_merge_topk's plus the column half of the threshold -- 32 bytes per source ROW
+ *   (row list 8, kept count 4, scan 8, threshold 8 + 4) and nothing per pair: there is no per-pair score array, every pass
+ *   over a row makes the scores it needs again.
+ * Returns 0; -1 and nothing changed (n_ops and n_dropped untouched) for an unknown rank and for smatrix_merge_topk's refusals. */
+enum { SMATRIX_RANK_VALUE = 0, SMATRIX_RANK_COSINE = 1 };
+int smatrix_merge_topk_by(smatrix_t* dst, smatrix_t* src, int op, int rank, uint32_t m, uint32_t min_value,
+                          uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped);
 int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr,
                        const uint32_t* pairs, uint64_t max_batch, uint64_t* n_ops);
 int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows,

@@ -80,6 +80,7 @@ def load():
         "smatrix_merge": (C.c_int, [H, H, C.c_int, C.c_uint64, u64p]),
         "smatrix_merge_scaled": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
         "smatrix_merge_topk": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
+        "smatrix_merge_topk_by": (C.c_int, [H, H, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
         "smatrix_import_csr": (C.c_int, [H, C.c_int, C.c_uint64, u32p, u64p, u32p, C.c_uint64, u64p]),
         "smatrix_import_csr_dev": (C.c_int, [H, C.c_int, C.c_uint64, V, V, V, C.c_uint64, u64p, V]),
         "smatrix_stats": (None, [H, C.POINTER(Stats)]),

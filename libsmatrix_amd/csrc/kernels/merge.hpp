@@ -558,6 +558,318 @@ __global__ __launch_bounds__(1024) void k_mgt_emit_big(const DirSlot* __restrict
   mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
 }
 
+// ---- smatrix_merge_topk_by, SMATRIX_RANK_COSINE: the m pairs of every row that SCORE best ------------------------------------
+// The score of the pair (y, v) of row x is k_cf_neighbors' (kernels/rows.hpp), expression for expression, in IEEE double:
+//   tb = get(y, 0), 0 counted as 1;  den = sqrt(get(x, 0)) * sqrt(tb);  score = den != 0 && !(v > den) ? v / den : 0
+// and the rank key is 96 bits, {the score's bit pattern, 0xFFFFFFFF - y}: larger is better -- by score (scores are >= 0: their
+// patterns order as they do), equal scores by ascending column; unique within a row.  A row without a head pair scores 0
+// everywhere and keeps its m lowest eligible columns; a dead cell scores 0.
+// The score is never stored per pair: every pass that needs it makes it again, each lane with its own neighbour's get(y, 0)
+// (apply_one<OP_GET>, as k_cf_neighbors: many independent look-ups in flight per wave).  The row's own total is read once per
+// row, and only in a row that has more than m eligible pairs.
+//   k_mgc_select       a wave per row of up to GETROW_WAVE_MAX cells.  One read counts the eligible pairs: a row of at most m is
+//                      done.  Otherwise a scoring pass ORs and ANDs the keys -- positive doubles share their top bytes, so the
+//                      passes start at the highest byte in which the row's keys DIFFER, with the bytes above it as the prefix --
+//                      and the MSB radix select of k_mgt_select runs over the 12 bytes, the 8 of the score and then the 4 of the
+//                      column; a bin of one key ends it.  A row of at most 128 cells (a lane holds two) keeps its two keys in
+//                      registers: ONE gather per pair for the whole selection.
+//   k_mgc_select_big   the longer rows, one 1024-lane workgroup per row over all its segments
+//   k_mgc_emit, k_mgc_emit_big<C>   the walkers with MgCos: the pair's score is made once more and compared with the row's
+//                      threshold {thr[r], thr_col[r]}; all zero = every eligible pair, and then nothing is gathered
+// Gathers per eligible pair of a row that is cut to m: 1 (OR / AND) + the passes + 1 (a bin of one key) + 1 (emission; 2 in a
+// row of two segments and more), or 1 + 1 in a row of at most 128 cells.
+struct MgcPair {                                           // the two cells a lane holds at one step, as rank keys
+  uint64_t s0, s1;                                         // score bits
+  uint32_t c0, c1;                                         // 0xFFFFFFFF - y
+  bool e0, e1;                                             // eligible
+};
+
+__device__ __forceinline__ uint64_t mgc_score_bits(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t y, uint32_t v) {
+  bool dummy = false;
+  uint32_t b_total = apply_one<OP_GET>(dir, dmask, arena, y, 0u, 0u, &dummy);
+  if (b_total == 0) b_total = 1;
+  const double num = (double)v;
+  const double den = sa * sqrt((double)b_total);
+  double score = 0.0;
+  if (den != 0.0 && !(num > den)) score = num / den;
+  return (uint64_t)__double_as_longlong(score);
+}
+
+__device__ __forceinline__ MgcPair mgc_keys(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t min_value, const uint4 q) {
+  MgcPair k{0, 0, ~q.x, ~q.z, mgt_eligible(q.x, q.y, min_value), mgt_eligible(q.z, q.w, min_value)};
+  if (k.e0) k.s0 = mgc_score_bits(dir, dmask, arena, sa, q.x, q.y);
+  if (k.e1) k.s1 = mgc_score_bits(dir, dmask, arena, sa, q.z, q.w);
+  return k;
+}
+
+// digit dg of the key: 11 .. 4 are the score's bytes 7 .. 0, 3 .. 0 the column key's
+__device__ __forceinline__ uint32_t mgc_digit(uint64_t s, uint32_t c, uint32_t dg) {
+  return dg >= 4 ? (uint32_t)(s >> (8 * (dg - 4))) & 255u : (c >> (8 * dg)) & 255u;
+}
+// the key agrees with the prefix in every digit above dg / down to dg (shifts in two steps: 56 + 8 is no shift by 64)
+__device__ __forceinline__ bool mgc_agrees_above(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
+  return dg >= 4 ? (((s ^ ps) >> (8 * (dg - 4))) >> 8) == 0 : s == ps && (((c ^ pc) >> (8 * dg)) >> 8) == 0;
+}
+__device__ __forceinline__ bool mgc_agrees_down(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
+  return dg >= 4 ? ((s ^ ps) >> (8 * (dg - 4))) == 0 : s == ps && ((c ^ pc) >> (8 * dg)) == 0;
+}
+// where the passes start, from the OR and the AND of two keys and more: the highest digit in which they differ (keys are
+// unique: there is one), and the digits above it -- common to all keys -- as the prefix
+__device__ __forceinline__ void mgc_start(uint64_t or_s, uint64_t and_s, uint32_t or_c, uint32_t and_c, uint32_t& dg, uint64_t& ps, uint32_t& pc) {
+  const uint64_t ds = or_s ^ and_s;
+  const uint32_t dc = or_c ^ and_c;
+  if (ds) {
+    const uint32_t sh = (63u - (uint32_t)__clzll((long long)ds)) & ~7u;
+    dg = 4 + (sh >> 3);
+    ps = ((and_s >> sh) >> 8) << 8 << sh;
+    pc = 0;
+  } else {
+    const uint32_t sh = dc ? (31u - (uint32_t)__clz((int)dc)) & ~7u : 0u;
+    dg = sh >> 3;
+    ps = and_s;
+    pc = ((and_c >> sh) >> 8) << 8 << sh;
+  }
+}
+__device__ __forceinline__ void mgc_take_digit(uint64_t& ps, uint32_t& pc, uint32_t dg, uint32_t d) {
+  if (dg >= 4) ps |= (uint64_t)d << (8 * (dg - 4));
+  else pc |= d << (8 * dg);
+}
+
+__device__ __forceinline__ uint32_t mg_wave_and(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v &= (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
+
+struct MgCosRow {
+  uint64_t thr;
+  uint32_t thr_col, min_value, dmask;
+  double sa;                                               // sqrt of the row's own total
+  DirSlot* dir;
+  uint8_t* arena;
+  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
+    if (val < min_value) return false;
+    if (key == 0) return val != 0;
+    if ((thr | thr_col) == 0) return true;
+    const uint64_t s = mgc_score_bits(dir, dmask, arena, sa, key, val);
+    return s > thr || (s == thr && ~key >= thr_col);
+  }
+};
+struct MgCos {
+  const uint64_t* thr;                                     // per row of the row list: the score bits of the m-th best key,
+  const uint32_t* thr_col;                                 // and its column half; both 0 = every eligible pair
+  const uint64_t* items;                                   // the row list (the row's directory slot in the high word)
+  DirSlot* dir;
+  uint8_t* arena;
+  uint32_t dmask, min_value;
+  __device__ __forceinline__ MgCosRow at(uint32_t r) const {
+    MgCosRow f{thr[r], thr_col[r], min_value, dmask, 0.0, dir, arena};
+    if (f.thr | f.thr_col) {                               // (a row that keeps all its eligible pairs scores nothing)
+      bool dummy = false;
+      f.sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, dir[(uint32_t)(items[r] >> 32)].x, 0u, 0u, &dummy));
+    }
+    return f;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_mgc_select(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t n,
+                                                    const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value,
+                                                    uint64_t* __restrict__ thr, uint32_t* __restrict__ thr_col,
+                                                    uint32_t* __restrict__ cnt, uint32_t* big, unsigned long long* tot) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][256];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t* hist = s_hist[threadIdx.x >> 6];
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  uint32_t seen = 0;
+  for (uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n; r += nwaves) {
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
+    if (size > GETROW_WAVE_MAX) {
+      if (lane == 0) big[1 + atomicAdd(&big[0], 1u)] = r;
+      continue;
+    }
+    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
+    auto fetch = [&](uint32_t p0) -> uint4 {               // (every lane takes every step: the steps hold ballots)
+      const uint32_t p = p0 + 2 * lane;
+      return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
+    };
+    uint32_t elig = 0, head = 0;
+    uint4 q0 = make_uint4(0, 0, 0, 0);                     // the lane's first two cells: all of a row of at most 128
+    for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+      const uint4 q = fetch(p0);
+      if (p0 == 0) q0 = q;
+      seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+      head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+      elig += mgt_eligible(q.x, q.y, min_value) + mgt_eligible(q.z, q.w, min_value);
+    }
+    elig = mg_wave_sum(elig);
+    head = mg_wave_or(head);
+    uint64_t ts = 0;
+    uint32_t tc = 0;
+    if (elig > m) {
+      bool dummy = false;
+      const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, s.y, 0u, 0u, &dummy));
+      const bool small = size <= 128;
+      MgcPair held{0, 0, 0, 0, false, false};
+      if (small) held = mgc_keys(dir, dmask, arena, sa, min_value, q0);
+      auto load = [&](uint32_t p0) -> MgcPair { return small ? held : mgc_keys(dir, dmask, arena, sa, min_value, fetch(p0)); };
+      uint32_t or_h = 0, or_l = 0, or_c = 0, and_h = ~0u, and_l = ~0u, and_c = ~0u;
+      for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+        const MgcPair k = load(p0);
+        if (k.e0) { or_h |= (uint32_t)(k.s0 >> 32); or_l |= (uint32_t)k.s0; or_c |= k.c0; and_h &= (uint32_t)(k.s0 >> 32); and_l &= (uint32_t)k.s0; and_c &= k.c0; }
+        if (k.e1) { or_h |= (uint32_t)(k.s1 >> 32); or_l |= (uint32_t)k.s1; or_c |= k.c1; and_h &= (uint32_t)(k.s1 >> 32); and_l &= (uint32_t)k.s1; and_c &= k.c1; }
+      }
+      uint32_t dg, need = m;
+      uint64_t ps;
+      uint32_t pc;
+      mgc_start(((uint64_t)mg_wave_or(or_h) << 32) | mg_wave_or(or_l), ((uint64_t)mg_wave_and(and_h) << 32) | mg_wave_and(and_l),
+                mg_wave_or(or_c), mg_wave_and(and_c), dg, ps, pc);
+      for (;;) {
+        for (uint32_t i = lane; i < 256; i += 64) hist[i] = 0;
+        mgt_wave_sync();
+        for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+          const MgcPair k = load(p0);
+          mgt_hist_add(hist, k.e0 && mgc_agrees_above(k.s0, k.c0, ps, pc, dg), mgc_digit(k.s0, k.c0, dg), lane);
+          mgt_hist_add(hist, k.e1 && mgc_agrees_above(k.s1, k.c1, ps, pc, dg), mgc_digit(k.s1, k.c1, dg), lane);
+        }
+        mgt_wave_sync();
+        uint32_t d, above, bucket;
+        mgt_pick<false>(hist, need, lane, d, above, bucket);
+        mgt_wave_sync();
+        need -= above;
+        mgc_take_digit(ps, pc, dg, d);
+        if (dg == 0) break;
+        if (bucket == 1) {                                 // the one key that agrees down to this digit
+          uint32_t hi = 0, lo = 0, col = 0;
+          for (uint32_t p0 = 0; p0 < size; p0 += 128) {
+            const MgcPair k = load(p0);
+            if (k.e0 && mgc_agrees_down(k.s0, k.c0, ps, pc, dg)) { hi |= (uint32_t)(k.s0 >> 32); lo |= (uint32_t)k.s0; col |= k.c0; }
+            if (k.e1 && mgc_agrees_down(k.s1, k.c1, ps, pc, dg)) { hi |= (uint32_t)(k.s1 >> 32); lo |= (uint32_t)k.s1; col |= k.c1; }
+          }
+          ps = ((uint64_t)mg_wave_or(hi) << 32) | mg_wave_or(lo);
+          pc = mg_wave_or(col);
+          break;
+        }
+        dg--;
+      }
+      ts = ps; tc = pc;
+    }
+    if (lane == 0) { thr[r] = ts; thr_col[r] = tc; cnt[r] = (elig < m ? elig : m) + head; }
+  }
+  seen = mg_wave_sum(seen);
+  if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+}
+
+__global__ __launch_bounds__(1024) void k_mgc_select_big(DirSlot* dir, uint32_t dmask, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                         uint32_t m, uint32_t min_value, uint64_t* __restrict__ thr,
+                                                         uint32_t* __restrict__ thr_col, uint32_t* __restrict__ cnt, const uint32_t* big,
+                                                         unsigned long long* tot) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ uint32_t wacc[6][16];                         // per wave: eligible, seen, head; then OR (hi, lo, col) and AND of the keys
+  __shared__ uint32_t acc[8];                              // 2 .. 4: the key found; 5 .. 7: d, above, bucket
+  auto uni = [&](uint32_t i) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)acc[i]); };   // (scalar control flow)
+  const uint32_t nent = big[0];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint32_t e = blockIdx.x; e < nent; e += gridDim.x) {
+    const uint32_t r = big[1 + e];
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = 1u << meta_lg(s.x);                          // > GETROW_WAVE_MAX: a multiple of 2048
+    const uint4* cells = reinterpret_cast<const uint4*>(row_cells(arena, s.z));
+    {
+      uint32_t elig = 0, seen = 0, head = 0;
+      for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+        const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+        seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+        head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+        elig += mgt_eligible(q.x, q.y, min_value) + mgt_eligible(q.z, q.w, min_value);
+      }
+      elig = mg_wave_sum(elig); seen = mg_wave_sum(seen); head = mg_wave_or(head);
+      if (lane == 0) { wacc[0][w] = elig; wacc[1][w] = seen; wacc[2][w] = head; }
+    }
+    __syncthreads();
+    uint32_t elig = 0, seen = 0, head = 0;
+    for (uint32_t i = 0; i < 16; i++) { elig += wacc[0][i]; seen += wacc[1][i]; head |= wacc[2][i]; }
+    elig = (uint32_t)__builtin_amdgcn_readfirstlane((int)elig);
+    if (threadIdx.x == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+    uint64_t ts = 0;
+    uint32_t tc = 0;
+    if (elig > m) {                                                    // (from LDS: the same on every lane)
+      bool dummy = false;
+      const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, s.y, 0u, 0u, &dummy));
+      __syncthreads();                                                 // (wacc was read by every lane)
+      {
+        uint32_t or_h = 0, or_l = 0, or_c = 0, and_h = ~0u, and_l = ~0u, and_c = ~0u;
+        for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+          const MgcPair k = mgc_keys(dir, dmask, arena, sa, min_value, cells[(p0 >> 1) + threadIdx.x]);
+          if (k.e0) { or_h |= (uint32_t)(k.s0 >> 32); or_l |= (uint32_t)k.s0; or_c |= k.c0; and_h &= (uint32_t)(k.s0 >> 32); and_l &= (uint32_t)k.s0; and_c &= k.c0; }
+          if (k.e1) { or_h |= (uint32_t)(k.s1 >> 32); or_l |= (uint32_t)k.s1; or_c |= k.c1; and_h &= (uint32_t)(k.s1 >> 32); and_l &= (uint32_t)k.s1; and_c &= k.c1; }
+        }
+        or_h = mg_wave_or(or_h); or_l = mg_wave_or(or_l); or_c = mg_wave_or(or_c);
+        and_h = mg_wave_and(and_h); and_l = mg_wave_and(and_l); and_c = mg_wave_and(and_c);
+        if (lane == 0) { wacc[0][w] = or_h; wacc[1][w] = or_l; wacc[2][w] = or_c; wacc[3][w] = and_h; wacc[4][w] = and_l; wacc[5][w] = and_c; }
+      }
+      __syncthreads();
+      uint32_t dg, need = m, pc;
+      uint64_t ps;
+      {
+        uint32_t or_h = 0, or_l = 0, or_c = 0, and_h = ~0u, and_l = ~0u, and_c = ~0u;
+        for (uint32_t i = 0; i < 16; i++) { or_h |= wacc[0][i]; or_l |= wacc[1][i]; or_c |= wacc[2][i]; and_h &= wacc[3][i]; and_l &= wacc[4][i]; and_c &= wacc[5][i]; }
+        auto sc = [](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+        mgc_start(((uint64_t)sc(or_h) << 32) | sc(or_l), ((uint64_t)sc(and_h) << 32) | sc(and_l), sc(or_c), sc(and_c), dg, ps, pc);
+      }
+      for (;;) {
+        __syncthreads();                                               // (acc and hist were read by every lane)
+        if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+          const MgcPair k = mgc_keys(dir, dmask, arena, sa, min_value, cells[(p0 >> 1) + threadIdx.x]);
+          mgt_hist_add(hist, k.e0 && mgc_agrees_above(k.s0, k.c0, ps, pc, dg), mgc_digit(k.s0, k.c0, dg), lane);
+          mgt_hist_add(hist, k.e1 && mgc_agrees_above(k.s1, k.c1, ps, pc, dg), mgc_digit(k.s1, k.c1, dg), lane);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+          uint32_t d, above, bucket;
+          mgt_pick<true>(hist, need, lane, d, above, bucket);
+          if (lane == 0) { acc[5] = d; acc[6] = above; acc[7] = bucket; }
+        }
+        __syncthreads();
+        need -= uni(6);
+        mgc_take_digit(ps, pc, dg, uni(5));
+        if (dg == 0) break;
+        if (uni(7) == 1) {
+          if (threadIdx.x < 3) acc[2 + threadIdx.x] = 0;
+          __syncthreads();
+          for (uint32_t p0 = 0; p0 < size; p0 += 2048) {               // (one lane of the workgroup: keys are unique)
+            const MgcPair k = mgc_keys(dir, dmask, arena, sa, min_value, cells[(p0 >> 1) + threadIdx.x]);
+            if (k.e0 && mgc_agrees_down(k.s0, k.c0, ps, pc, dg)) { acc[2] = (uint32_t)(k.s0 >> 32); acc[3] = (uint32_t)k.s0; acc[4] = k.c0; }
+            if (k.e1 && mgc_agrees_down(k.s1, k.c1, ps, pc, dg)) { acc[2] = (uint32_t)(k.s1 >> 32); acc[3] = (uint32_t)k.s1; acc[4] = k.c1; }
+          }
+          __syncthreads();
+          ps = ((uint64_t)uni(2) << 32) | uni(3);
+          pc = uni(4);
+          break;
+        }
+        dg--;
+      }
+      ts = ps; tc = pc;
+    }
+    if (threadIdx.x == 0) { thr[r] = ts; thr_col[r] = tc; cnt[r] = (elig < m ? elig : m) + head; }
+    __syncthreads();                                                   // (wacc and acc are the next row's)
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mgc_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgCos f) {
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, f);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mgc_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                       const uint32_t* big, uint32_t* seg_cnt, const MgCos f) {
+  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
+}
+
 // ---- from a CSR in smatrix_export's layout ------------------------------------------------------------------------------------
 // k_mg_csr_check: *bad |= 1 unless row_ptr[0] == 0 and row_ptr[i] <= row_ptr[i + 1] for every i < n_rows (before the first write)
 __global__ __launch_bounds__(256) void k_mg_csr_check(uint64_t n_rows, const uint64_t* __restrict__ row_ptr, uint32_t* bad) {

@@ -1,5 +1,5 @@
-// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_import_csr / smatrix_import_csr_dev (include/smatrix_batch.h),
-// host side.
+// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_merge_topk_by / smatrix_import_csr /
+// smatrix_import_csr_dev (include/smatrix_batch.h), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_row_list, ex_measure
 // and scan); the device code is kernels/merge.hpp.
 //
@@ -21,6 +21,8 @@
 //        the same scan, so the cuts and the rows' record offsets are those of what k_mgx_emit* will write; same memory.
 // merge_topk: the same with the counts and an 8-byte threshold per row from the selection (k_mgt_select*); the emission filters
 //        by that threshold (k_mgt_emit*) and counts a cut row's segments batch by batch, as merge does.  28 bytes per row.
+// merge_topk_by, SMATRIX_RANK_COSINE: merge_topk with the selection and the emission of the cosine rank (k_mgc_*): the threshold
+//        is 12 bytes per row, its score half in thr and its column half in thr_col.  32 bytes per row, no score per pair.
 
 namespace {
 
@@ -28,7 +30,7 @@ constexpr uint64_t MG_DEFAULT_BATCH = 1ull << 24;      // the batch size the wri
 constexpr uint64_t MG_MAX_BATCH = 1ull << 31;          // (a write batch holds fewer than 2^32 ops)
 
 struct MergeScratch {
-  DevBuf<uint32_t> rec[2], big, seg_cnt, flag, h_rows, h_pairs[2];
+  DevBuf<uint32_t> rec[2], big, seg_cnt, flag, h_rows, h_pairs[2], thr_col;   // thr_col: the column half of a cosine threshold
   DevBuf<uint64_t> ptr, h_ptr, thr;                      // thr: merge_topk's per-row rank-key thresholds
   DevBuf<unsigned long long> tot;                        // merge_scaled: the candidates the count kernels saw
   hipStream_t e = nullptr;                               // the helper stream: emission
@@ -52,7 +54,7 @@ MergeScratch& mg_of(Matrix* m) {
 void mg_trim_all(MergeScratch& g, bool all) {
   ex_trim(g.rec[0], all); ex_trim(g.rec[1], all); ex_trim(g.big, all); ex_trim(g.seg_cnt, all); ex_trim(g.flag, all);
   ex_trim(g.h_rows, all); ex_trim(g.h_pairs[0], all); ex_trim(g.h_pairs[1], all); ex_trim(g.ptr, all); ex_trim(g.h_ptr, all);
-  ex_trim(g.tot, all); ex_trim(g.thr, all);
+  ex_trim(g.tot, all); ex_trim(g.thr, all); ex_trim(g.thr_col, all);
 }
 
 void merge_release(Matrix* m) {
@@ -347,6 +349,35 @@ int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint3
       mg_emit(c, k_mgt_emit, r0, r1, rec, e, f);
       mg_emit_big(c, k_mgt_emit_big<true>, r0, rec, e, f);
       mg_emit_big(c, k_mgt_emit_big<false>, r0, rec, e, f);
+    });
+}
+
+int smatrix_merge_topk_by(smatrix_t* dst, smatrix_t* src, int op, int rank, uint32_t m, uint32_t min_value, uint64_t max_batch,
+                          uint64_t* n_ops, uint64_t* n_dropped) {
+  if (rank == SMATRIX_RANK_VALUE) return smatrix_merge_topk(dst, src, op, m, min_value, max_batch, n_ops, n_dropped);
+  if (rank != SMATRIX_RANK_COSINE || m == 0) return -1;
+  return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
+    [&](MergeCall& c) {
+      // merge_topk's count stage with the cosine selection: the kept counts in x.cnt, the thresholds in thr and thr_col
+      mg_count_filtered(c, true,
+        [&] {
+          c.g.thr.need(c.n);
+          c.g.thr_col.need(c.n);
+          hipLaunchKernelGGL(k_mgc_select, dim3(mg_row_grid(c.n)), dim3(256), 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base,
+                             (uint32_t)c.n, c.x.items.p, m, min_value, c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+          hipLaunchKernelGGL(k_mgc_select_big, dim3(c.big_grid), dim3(1024), 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base,
+                             c.x.items.p, m, min_value, c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+        },
+        [&](float sel, float cnt) {
+          fprintf(stderr, "[smatrix] merge_topk_by cosine: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
+                  sel, cnt, (unsigned long long)c.kept, c.seen);
+        });
+    },
+    [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      const MgCos f{c.g.thr.p, c.g.thr_col.p, c.x.items.p, c.sm->d_dir, c.sm->arena.base, c.sm->dir_size - 1, min_value};
+      mg_emit(c, k_mgc_emit, r0, r1, rec, e, f);
+      mg_emit_big(c, k_mgc_emit_big<true>, r0, rec, e, f);
+      mg_emit_big(c, k_mgc_emit_big<false>, r0, rec, e, f);
     });
 }
 

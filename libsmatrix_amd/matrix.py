@@ -56,6 +56,20 @@ def _topk_args(m, min_value):
     _check_u32("min_value", min_value)
 
 
+_RANKS = {"value": 0, "cosine": 1}                      # SMATRIX_RANK_VALUE, SMATRIX_RANK_COSINE
+
+
+def _rank(rank):
+    """"value" / "cosine" -> the rank code; anything else is a ValueError"""
+    if isinstance(rank, str) and rank in _RANKS:
+        return _RANKS[rank]
+    raise ValueError("rank must be 'value' or 'cosine', not %r" % (rank,))
+
+
+def _topk_by_args(rank, m, min_value):
+    _topk_args(m, min_value)
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -374,18 +388,27 @@ class SparseMatrix:
         _scale_args(num, den, min_value)
         return self._copy_by(SparseMatrix.merge_scaled, filename, "set", num, den, min_value)
 
-    def merge_topk(self, other, m, op="set", min_value=1, max_batch=0):
+    def merge_topk(self, other, m, op="set", min_value=1, max_batch=0, rank="value"):
         """merge that keeps the m heaviest pairs of every row of other: of the pairs (y != 0, v >= min_value) those of the largest
         v, equal values by ascending column; the column-0 pair (the CF total) is kept beside them when v >= min_value.  The kept
-        pairs are applied as self[x, y] op= v.  1 <= m <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified."""
-        return self._merge_call("merge_topk", other, op, m, min_value, check=_topk_args, max_batch=max_batch)
+        pairs are applied as self[x, y] op= v.  1 <= m <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified.
+        rank="cosine" (smatrix_merge_topk_by): the m pairs that SCORE best in cf_neighbors_batch / cf_topk_batch /
+        cf_recommend_batch, v / (sqrt(other[x, 0]) * sqrt(other[y, 0])) with their guards, equal scores by ascending column;
+        the values applied are still the raw v."""
+        r = _rank(rank)
+        if r == 0:
+            return self._merge_call("merge_topk", other, op, m, min_value, check=_topk_args, max_batch=max_batch)
+        return self._merge_call("merge_topk_by", other, op, r, m, min_value, check=_topk_by_args, max_batch=max_batch)
 
-    def truncated(self, m, min_value=1, filename=None):
+    def truncated(self, m, min_value=1, filename=None, rank="value"):
         """a NEW matrix (in memory, or file-backed when filename is given) that holds, of every row of self, the m heaviest pairs
         of at least min_value and the column-0 pair: at most m + 1 pairs per row, the serving copy of an item-kNN recommender
-        (total += today; total -= day_30; serving = total.truncated(m)).  self is not modified."""
+        (total += today; total -= day_30; serving = total.truncated(m)).  self is not modified.
+        rank="cosine": the m best-scoring pairs instead of the m heaviest, so that the copy's cf_topk_batch(items, k <= m)
+        returns the scores self's does."""
+        _rank(rank)
         _topk_args(m, min_value)
-        return self._copy_by(SparseMatrix.merge_topk, filename, m, "set", min_value)
+        return self._copy_by(SparseMatrix.merge_topk, filename, m, "set", min_value, 0, rank)
 
     def __iadd__(self, other):
         if not isinstance(other, SparseMatrix):
