@@ -123,6 +123,39 @@ int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_
 int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
                                    uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
 
+/* Session recommendations with "not these" and recency: smatrix_cf_recommend_batch with per-position weights, a per-session
+ * exclusion list (a user's own history) and a deny bitmap for all sessions (out of stock, delisted), all applied on the GPU
+ * BEFORE the k best are taken, so k valid results come back however many candidates are filtered.  What is not said here is
+ * smatrix_cf_recommend_batch's contract; with weights, ex_offsets, ex_items, deny_bits NULL and deny_n 0 the call writes its bytes.
+ *   weights    NULL (every weight 1.0), or one double per entry of items: weights[offsets[s] + i] belongs to
+ *              items[offsets[s] + i].  A distinct item has the weight at its FIRST position; later occurrences are ignored,
+ *              weight included.  score(b) = the left-to-right sum from 0.0, in session order, of w_a * cf_cosine(a, b), the
+ *              product rounded to double on its own before it is added; w == 1.0 gives the unweighted bytes.  Every weight
+ *              must be finite and >= 0 (-0.0 acts as 0.0).  An item of weight 0 is still an item of the session: it is not
+ *              recommended, and the keys of its row are candidates with a term of 0.0.
+ *   ex_*       both NULL, or ex_offsets has n_sessions + 1 entries and session s is never given
+ *              ex_items[ex_offsets[s] .. ex_offsets[s+1]) (fewer than 2^32 ids a list).  An id may be repeated, 0 or absent
+ *              from the matrix (no effect), or an item of the session, which stays an item: its row is scanned and its
+ *              weight counts.  The rows of excluded ids are not read.
+ *   deny_*     deny_bits NULL with deny_n == 0, or a bitmap over the ids 0 .. deny_n - 1 (deny_n <= 2^32, (deny_n + 31) / 32
+ *              words): id b < deny_n is denied when bit b & 31 of word b >> 5 is set, ids >= deny_n are allowed.  A denied id
+ *              is given to no session; as an item of a session it contributes like any other.
+ *   counts     excluded and denied ids do not count: counts[s] = min(k, candidates left).
+ * Returns -1 for k == 0, k > 64, n_sessions >= 2^32, deny_n > 2^32, deny_bits NULL with deny_n != 0, exactly one of ex_offsets /
+ * ex_items NULL, or a weight that is negative, NaN or infinite: the host flavour checks the weights before it touches the device
+ * and leaves the outputs as they were, _dev finds them on the device and leaves the outputs' contents unspecified.  0 otherwise.
+ * Memory beyond smatrix_cf_recommend_batch's: one more slot per exclusion-list entry in the session's table (a session's table
+ * has room for its candidates, its items and its list, so a small session with a long list is summed in device memory, 20
+ * bytes a slot, not in LDS); the host flavour also holds device copies of the three inputs for the call. */
+int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                  const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                                  const uint32_t* deny_bits, uint64_t deny_n, uint32_t k, uint32_t* ids, double* scores,
+                                  uint32_t* counts);
+int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                      const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                      const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids,
+                                      double* d_scores, uint32_t* d_counts, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

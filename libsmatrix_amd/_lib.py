@@ -73,6 +73,9 @@ def load():
         "smatrix_cf_topk_batch_dev": (C.c_int, [H, C.c_size_t, V, C.c_uint32, V, V, V, V]),
         "smatrix_cf_recommend_batch": (C.c_int, [H, C.c_size_t, u64p, u32p, C.c_uint32, u32p, C.POINTER(C.c_double), u32p]),
         "smatrix_cf_recommend_batch_dev": (C.c_int, [H, C.c_size_t, V, V, C.c_uint32, V, V, V, V]),
+        "smatrix_cf_recommend_filtered": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64,
+                                                    C.c_uint32, u32p, C.POINTER(C.c_double), u32p]),
+        "smatrix_cf_recommend_filtered_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, C.c_uint32, V, V, V, V]),
         "smatrix_cf_import_sessions": (C.c_int, [H, C.c_size_t, u64p, u32p]),
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
         "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),

@@ -13,6 +13,11 @@
 //   k_rec_lds       a workgroup per session of bound + length <= REC_LDS_SLOTS: the hash in LDS, the top-k at the end
 //   k_rec_gl_*      the other sessions: hashes in a pooled device buffer, a launch per item position, a wave per 512-cell chunk
 //                   of a row; then a wave per 4096-slot segment (its top-64) and a workgroup per session (the merge)
+// smatrix_cf_recommend_filtered (RecFilt, the kernels' <true> instances; <false> is smatrix_cf_recommend_batch's code):
+//   exclusion list  more excluded keys, entered with the session's items (sqrt = -1; the low word of the sum is left alone: it is
+//                   an ITEM's first position, and an id may be both); the table has room for them (k_rec_bound)
+//   deny bitmap     tested where a key is claimed: a denied key gets sqrt = -1 like an item
+//   weights         the term of the item at position i is multiplied by w[i] (__dmul_rn: rounded on its own) before it is added
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -22,9 +27,22 @@ constexpr uint32_t REC_CHUNK = 512;           // global tier: cells of a row per
 constexpr uint32_t REC_MERGE_THREADS = 1024;
 
 struct RecCtl {
-  uint32_t n_lds, n_big, max_len, pad;
+  uint32_t n_lds, n_big, max_len, bad;        // bad: a weight that is negative, NaN or infinite (k_rec_bound<true>)
   unsigned long long total_slots, max_slots;  // global tier: table slots of all its sessions, of the largest one
 };
+
+// what smatrix_cf_recommend_filtered adds; every pointer may be NULL (not given), deny == NULL goes with deny_n == 0
+struct RecFilt {
+  const double* w;                            // per entry of items
+  const uint64_t* ex_off;                     // session s must not be given ex[ex_off[s] .. ex_off[s+1])
+  const uint32_t* ex;
+  const uint32_t* deny;                       // bit b & 31 of word b >> 5: id b < deny_n is never given
+  uint64_t deny_n;
+};
+__device__ __forceinline__ bool rec_denied(const RecFilt& f, uint32_t b) {
+  return b < f.deny_n && ((f.deny[b >> 5] >> (b & 31)) & 1u) != 0;
+}
+__device__ __forceinline__ bool rec_weight_ok(double w) { return w >= 0.0 && w <= 1.7976931348623157e308; }   // (-0.0 passes, NaN fails)
 
 // (score desc, id asc): the result order of smatrix_cf_recommend_batch
 struct CfById {
@@ -83,13 +101,16 @@ __device__ __forceinline__ uint32_t rec_low_word(const double* p) { return *rein
 // cut to all_cells, the cells the arena can hold (no session has more candidates than the matrix has cells).  A table never
 // needs more than 2^32 slots: its keys are distinct non-zero 32-bit ids.
 // A session with no row at all has no candidate: its count is written here.  tlg[s] = log2 of the session's table size.
+// <true>: the table also holds the E ids of the session's exclusion list (a repeated id only wastes a slot), so the tier is chosen
+// on bound + L + E; every weight of the session is checked (ctl->bad).
 constexpr uint64_t REC_DEDUP_MAX = 8192;
 constexpr uint32_t REC_MAX_LG = 32;
 
+template <bool F>
 __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask, uint32_t n, const uint64_t* __restrict__ off,
                                                    const uint32_t* __restrict__ items, uint64_t all_cells, RecCtl* ctl,
                                                    uint32_t* lds_list, uint8_t* tlg, uint32_t* big_list, unsigned long long* big_off,
-                                                   uint32_t* __restrict__ counts) {
+                                                   uint32_t* __restrict__ counts, RecFilt f) {
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t s = wave; s < n; s += nwaves) {
@@ -99,6 +120,7 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
     for (uint64_t c0 = 0; c0 < L; c0 += 64) {                       // (wave-uniform loops: the shuffles need every lane)
       const uint64_t i = c0 + lane;
       const uint32_t a = i < L ? items[b0 + i] : 0u;
+      if (F && f.w && i < L && !rec_weight_ok(f.w[b0 + i])) ctl->bad = 1u;
       uint64_t sz = 0;
       uint4 sn;
       if (i < L && dir_find(dir, dmask, a, &sn) && sn.z != 0) sz = 1ull << meta_lg(sn.x);
@@ -121,6 +143,7 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
     if (bound == 0) { counts[s] = 0; continue; }
     if (bound > all_cells) bound = all_cells;
     uint64_t need = bound + L;
+    if (F && f.ex_off) need += f.ex_off[s + 1] - f.ex_off[s];
     if (need > (1ull << REC_MAX_LG)) need = 1ull << REC_MAX_LG;
     if (need <= REC_LDS_SLOTS) {
       tlg[s] = (uint8_t)rec_lg(need, 6);
@@ -138,11 +161,12 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 }
 
 // ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
+template <bool F>
 __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
                                                              const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
                                                              const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
                                                              uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
-                                                             uint32_t* __restrict__ counts) {
+                                                             uint32_t* __restrict__ counts, RecFilt f) {
   __shared__ uint32_t s_key[REC_LDS_SLOTS];
   __shared__ double s_sq[REC_LDS_SLOTS];
   __shared__ double s_sum[REC_LDS_SLOTS];
@@ -165,6 +189,15 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
       s_sq[h] = -1.0;
       atomicMax(reinterpret_cast<uint32_t*>(&s_sum[h]), rec_first_word(i));
     }
+    if (F && f.ex_off) {                                            // the exclusion list: excluded, and no more
+      const uint64_t e0 = f.ex_off[s], E = f.ex_off[s + 1] - e0;
+      for (uint64_t i = tid; i < E; i += REC_LDS_THREADS) {
+        const uint32_t a = f.ex[e0 + i];
+        if (a == 0) continue;
+        bool claimed;
+        s_sq[rec_slot<true>(s_key, mask, a, &claimed)] = -1.0;
+      }
+    }
     __syncthreads();
     bool seen0 = false;                                             // (item 0 is never a key: its duplicates are told here)
     for (uint32_t i = 0; i < L; i++) {                              // session order; everything up to the scan is uniform
@@ -179,6 +212,7 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
       if (!dir_find(dir, dmask, a, &sn) || sn.z == 0) continue;
       bool dummy = false;
       const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+      const double wa = F && f.w ? f.w[b0 + i] : 1.0;
       const uint32_t size = 1u << meta_lg(sn.x);
       const uint64_t* cells = row_cells(arena, sn.z);
       for (uint32_t p = tid; p < size; p += REC_LDS_THREADS) {
@@ -189,14 +223,19 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
         const uint32_t h = rec_slot<true>(s_key, mask, b, &claimed);
         double sqb;
         if (claimed) {
+          if (F && rec_denied(f, b)) { s_sq[h] = -1.0; continue; }  // a denied key: excluded from here on
           sqb = rec_sqrt_total(dir, dmask, arena, b);
           s_sq[h] = sqb;
         } else {
           sqb = s_sq[h];
-          if (sqb < 0.0) continue;                                  // an item of the session
-          if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);   // claimed by another lane of this row (a twice-held key)
+          if (sqb < 0.0) continue;                                  // an item of the session, an excluded or a denied key
+          // claimed by another lane of this row (a twice-held key).  If that lane is about to deny the key, this term is added
+          // to a sum nobody reads: the selection below takes s_sq > 0 after the barrier
+          if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);
         }
-        __hip_atomic_fetch_add(&s_sum[h], rec_term(cell_val(c), sa, sqb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        double term = rec_term(cell_val(c), sa, sqb);
+        if (F) term = __dmul_rn(wa, term);                          // (rounded before the add; wa == 1.0 changes no bit)
+        __hip_atomic_fetch_add(&s_sum[h], term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
       __syncthreads();
     }
@@ -263,8 +302,11 @@ __device__ __forceinline__ bool rec_in_group(const RecGl& R, uint32_t idx, uint6
   return true;
 }
 
-// a workgroup per session: the items as excluded keys, item 0's first position, the owners of the table's segments
-__global__ __launch_bounds__(256) void k_rec_gl_init(RecGl R, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items) {
+// a workgroup per session: the items as excluded keys, item 0's first position, the owners of the table's segments;
+// <true>: the exclusion list as excluded keys
+template <bool F>
+__global__ __launch_bounds__(256) void k_rec_gl_init(RecGl R, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                     RecFilt f) {
   for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
     uint64_t loc;
     if (!rec_in_group(R, idx, &loc)) continue;
@@ -279,6 +321,15 @@ __global__ __launch_bounds__(256) void k_rec_gl_init(RecGl R, const uint64_t* __
       const uint32_t h = rec_slot<false>(keys, (uint32_t)(tsize - 1), a, &claimed);
       R.gq[loc + h] = -1.0;
       atomicMax(reinterpret_cast<uint32_t*>(&R.gs[loc + h]), rec_first_word(i));
+    }
+    if (F && f.ex_off) {
+      const uint64_t e0 = f.ex_off[s], E = f.ex_off[s + 1] - e0;
+      for (uint64_t i = threadIdx.x; i < E; i += blockDim.x) {
+        const uint32_t a = f.ex[e0 + i];
+        if (a == 0) continue;
+        bool claimed;
+        R.gq[loc + rec_slot<false>(keys, (uint32_t)(tsize - 1), a, &claimed)] = -1.0;
+      }
     }
   }
 }
@@ -308,9 +359,10 @@ __global__ __launch_bounds__(256) void k_rec_gl_plan(RecGl R, DirSlot* dir, uint
 }
 
 // position p = p0 + j: a wave per chunk task; scan[j * n_big + idx] = the first task of session idx (scan of k_rec_gl_plan's counts)
+template <bool F>
 __global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
                                                      const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
-                                                     uint32_t j, const uint64_t* __restrict__ scan) {
+                                                     uint32_t j, const uint64_t* __restrict__ scan, RecFilt f) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
   const uint64_t* sc = scan + (uint64_t)j * R.n_big;
@@ -328,6 +380,7 @@ __global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint
     dir_find(dir, dmask, a, &sn);                                   // (there: the plan gave it chunks)
     bool dummy = false;
     const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+    const double wa = F && f.w ? f.w[off[s] + p0 + j] : 1.0;
     const uint32_t size = 1u << meta_lg(sn.x);
     const uint64_t* cells = row_cells(arena, sn.z);
     uint32_t* keys = R.gk + loc;
@@ -347,14 +400,17 @@ __global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint
       const uint32_t h = rec_slot<false>(keys, mask, b, &claimed);
       double sqb;
       if (claimed) {
+        if (F && rec_denied(f, b)) { sq[h] = -1.0; continue; }
         sqb = rec_sqrt_total(dir, dmask, arena, b);
         sq[h] = sqb;
       } else {
         sqb = __hip_atomic_load(&sq[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (sqb < 0.0) continue;
-        if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);
-      }
-      unsafeAtomicAdd(&sum[h], rec_term(cell_val(cv[u]), sa, sqb));
+        if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);   // (a denied key's claimer may be between its claim and its
+      }                                                               // store: as in k_rec_lds, k_rec_gl_topk reads gq > 0 later)
+      double term = rec_term(cell_val(cv[u]), sa, sqb);
+      if (F) term = __dmul_rn(wa, term);
+      unsafeAtomicAdd(&sum[h], term);
     }
   }
 }

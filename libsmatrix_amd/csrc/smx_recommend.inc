@@ -1,4 +1,5 @@
-// smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev), host side.
+// smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev and
+// smatrix_cf_recommend_filtered / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -8,6 +9,8 @@
 //   3. the global tier, per group of sessions whose tables fit REC_GROUP_SLOTS (normally one group): zeroed tables, k_rec_gl_init,
 //      per block of item positions the chunk counts (k_rec_gl_plan) and their scan, a k_rec_gl_scan launch per position (the
 //      kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
+// The filtered call is the same driver with a RecFilt (weights, exclusion lists, deny bitmap) and the kernels' <true> instances;
+// with nothing given it runs the <false> ones, the code of smatrix_cf_recommend_batch.
 
 namespace {
 
@@ -24,7 +27,9 @@ struct RecScratch {
   DevBuf<uint64_t> scan, part;
   DevBuf<uint32_t> h_items, h_ids, h_counts;         // the host flavour's device copies of the caller's arrays
   DevBuf<uint64_t> h_off;
-  DevBuf<double> h_scores;
+  DevBuf<double> h_scores, h_w;                      // ... and the filtered call's: weights, exclusion lists, deny bitmap
+  DevBuf<uint64_t> h_exoff;
+  DevBuf<uint32_t> h_ex, h_deny;
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
 };
 
@@ -43,7 +48,8 @@ void rec_trim_all(RecScratch& x, bool all) {
   rec_trim(x.ctl, all); rec_trim(x.lds_list, all); rec_trim(x.big_list, all); rec_trim(x.gk, all); rec_trim(x.owner, all);
   rec_trim(x.zpos, all); rec_trim(x.cnt, all); rec_trim(x.li, all); rec_trim(x.big_off, all); rec_trim(x.tlg, all); rec_trim(x.gq, all);
   rec_trim(x.gs, all); rec_trim(x.lk, all); rec_trim(x.scan, all); rec_trim(x.part, all); rec_trim(x.h_items, all); rec_trim(x.h_ids, all);
-  rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all);
+  rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all); rec_trim(x.h_w, all); rec_trim(x.h_exoff, all);
+  rec_trim(x.h_ex, all); rec_trim(x.h_deny, all);
 }
 
 bool rec_any_big(const RecScratch& x) {
@@ -72,24 +78,27 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
   HIP_OK(hipGetLastError());
 }
 
-// the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back)
-void rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-             uint32_t* d_ids, double* d_scores, uint32_t* d_counts) {
+// the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back).
+// F: the filtered call with something given in f.  -1 (nothing but k_rec_bound has run) for a bad weight, 0 otherwise
+template <bool F>
+int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f) {
   DirSlot* dir = m->d_dir;
   const uint32_t dmask = m->dir_size - 1;
   x.ctl.need(1); x.lds_list.need(n); x.big_list.need(n); x.big_off.need(n); x.tlg.need(n);
   HIP_OK(hipMemsetAsync(x.ctl.p, 0, sizeof(RecCtl), s));
-  hipLaunchKernelGGL(k_rec_bound, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, d_off,
-                     d_items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, d_counts);
+  hipLaunchKernelGGL(k_rec_bound<F>, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, d_off,
+                     d_items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, d_counts, f);
   HIP_OK(hipGetLastError());
   RecCtl c;
   HIP_OK(hipMemcpyAsync(&c, x.ctl.p, sizeof c, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
+  if (F && c.bad) return -1;
   if (c.n_lds)
-    hipLaunchKernelGGL(k_rec_lds, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
-                       x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts);
+    hipLaunchKernelGGL(k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
+                       x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
   HIP_OK(hipGetLastError());
-  if (!c.n_big) return;
+  if (!c.n_big) return 0;
   const uint64_t ngroups = (c.total_slots + REC_GROUP_SLOTS - 1) / REC_GROUP_SLOTS;
   const uint64_t cap = ngroups == 1 ? c.total_slots : REC_GROUP_SLOTS + c.max_slots;
   const uint64_t nseg = cap / REC_SEG;
@@ -105,7 +114,7 @@ void rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t
     HIP_OK(hipMemsetAsync(x.gs.p, 0, ext * 8, s));
     HIP_OK(hipMemsetAsync(x.owner.p, 0xff, nseg * 4, s));
     HIP_OK(hipMemsetAsync(x.zpos.p, 0, (size_t)c.n_big * 4, s));
-    hipLaunchKernelGGL(k_rec_gl_init, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, R, d_off, d_items);
+    hipLaunchKernelGGL(k_rec_gl_init<F>, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, R, d_off, d_items, f);
     HIP_OK(hipGetLastError());
     for (uint32_t p0 = 0; p0 < c.max_len; p0 += np) {
       const uint32_t nj = std::min<uint32_t>(np, c.max_len - p0);
@@ -114,7 +123,8 @@ void rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t
       HIP_OK(hipGetLastError());
       rec_scan(x, s, x.cnt.p, nt, x.scan.p);
       for (uint32_t j = 0; j < nj; j++)
-        hipLaunchKernelGGL(k_rec_gl_scan, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off, d_items, p0, j, x.scan.p);
+        hipLaunchKernelGGL(k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off, d_items, p0, j, x.scan.p,
+                           f);
       HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, R, nseg, k, x.lk.p,
@@ -123,7 +133,17 @@ void rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t
                        d_ids, d_scores, d_counts);
     HIP_OK(hipGetLastError());
   }
+  return 0;
 }
+
+// what both flavours of the filtered call refuse before anything else
+bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n,
+                      uint32_t k) {
+  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return false;
+  if (deny_n > (1ull << 32) || (!deny_bits && deny_n)) return false;
+  return (ex_offsets == nullptr) == (ex_items == nullptr);
+}
+bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
 
 void recommend_release(Matrix* m) {
   if (!m->rec) return;
@@ -149,7 +169,7 @@ int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uin
   hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
   RecScratch& x = rec_of(m);
   rec_begin(x, s);
-  rec_run(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts);
+  rec_run<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{});
   rec_end(x, s);
   if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
   rec_trim_all(x, false);
@@ -175,7 +195,83 @@ int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_
   if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as cf_topk_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_run(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p);
+  rec_run<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{});
+  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
+  rec_end(x, s);
+  HIP_OK(hipStreamSynchronize(s));
+  rec_trim_all(x, false);
+  return 0;
+}
+
+int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                      const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                      const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids, double* d_scores,
+                                      uint32_t* d_counts, void* hip_stream) {
+  if (!rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
+  if (n_sessions == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n};
+  const int rc = rec_filt_any(f) ? rec_run<true>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f)
+                                 : rec_run<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f);
+  rec_end(x, s);
+  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
+  rec_trim_all(x, false);
+  return rc;
+}
+
+int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                  const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                                  const uint32_t* deny_bits, uint64_t deny_n, uint32_t k, uint32_t* ids, double* scores,
+                                  uint32_t* counts) {
+  if (!rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
+  if (n_sessions == 0) return 0;
+  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
+  if (weights)
+    for (uint64_t i = 0; i < n_items; i++)
+      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = m->stream;
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
+  std::vector<uint64_t> rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
+  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
+  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
+  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
+  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
+  RecFilt f{};
+  if (weights) {
+    x.h_w.need(std::max<uint64_t>(n_items, 1));
+    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
+    f.w = x.h_w.p;
+  }
+  if (ex_offsets) {
+    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
+    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
+    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
+  }
+  if (deny_n) {
+    x.h_deny.need(n_deny);
+    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
+    f.deny = x.h_deny.p; f.deny_n = deny_n;
+  }
+  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as smatrix_cf_recommend_batch's
+  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
+  if (rec_filt_any(f)) rec_run<true>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
+  else rec_run<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
   HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));

@@ -84,6 +84,29 @@ def _check_k(k):
         raise ValueError("k must be 1..64, not %r" % (k,))
 
 
+def _weights(weights, sessions):
+    """per-session weight sequences shaped like sessions -> float64[total]; a shape that differs, a negative or a non-finite
+    weight is a ValueError"""
+    if len(weights) != len(sessions) or any(len(w) != len(s) for w, s in zip(weights, sessions)):
+        raise ValueError("weights must hold one sequence per session, of the session's length")
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(w, dtype=np.float64) for w in weights]) if len(weights)
+                                else np.zeros(0, np.float64))
+    if not (np.isfinite(flat) & (flat >= 0)).all():
+        raise ValueError("weights must be finite and >= 0")
+    return flat
+
+
+def _deny_bitmap(deny):
+    """a sequence of ids -> (bitmap uint32[(deny_n + 31) / 32], deny_n = the largest id + 1); (None, 0) for no id"""
+    ids = np.unique(_u32(deny))
+    if ids.size == 0:
+        return None, 0
+    deny_n = int(ids[-1]) + 1
+    bits = np.zeros((deny_n + 31) // 32, dtype=np.uint32)
+    np.bitwise_or.at(bits, ids >> 5, np.uint32(1) << (ids & np.uint32(31)))
+    return bits, deny_n
+
+
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
@@ -259,6 +282,42 @@ class SparseMatrix:
         sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
+
+    def cf_recommend_filtered(self, sessions, k, weights=None, exclude=None, deny=None):
+        """cf_recommend_batch with "not these" and recency (include/smatrix_batch.h smatrix_cf_recommend_filtered), applied on
+        the GPU before the k best are taken.  weights: per-session sequences shaped like sessions, finite and >= 0 (the term of
+        an item is multiplied by the weight at its first position); exclude: one id sequence per session, never given to it;
+        deny: ids given to no session.  -> (ids[n,k], scores[n,k] float64, counts[n]) as cf_recommend_batch"""
+        _check_k(k)
+        n = len(sessions)
+        w = None if weights is None else _weights(weights, sessions)
+        if exclude is not None and len(exclude) != n:
+            raise ValueError("exclude must hold one id sequence per session")
+        offsets, items = _sessions(sessions)
+        ex_off, ex = _sessions(exclude) if exclude is not None else (None, None)
+        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        ids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        if n and self._lib.smatrix_cf_recommend_filtered(
+                self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
+                None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
+                None if bits is None else _p(bits), deny_n, k, ids.ctypes.data_as(_lib.u32p), scores.ctypes.data_as(dp),
+                _p(counts)) != 0:
+            raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
+        return ids, scores, counts
+
+    def cf_recommend_filtered_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, k, ids_ptr,
+                                  scores_ptr, cnt_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given): cf_recommend_batch_dev's, and weights
+        float64 per item, ex_off uint64[n+1], ex_items uint32, deny uint32[(deny_n + 31) / 32].  A bad weight is found on the
+        device: ValueError, the outputs' contents unspecified"""
+        _check_k(k)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_filtered_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
+                                                       deny_n, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_filtered_dev: bad k, n, weights, exclusion lists or deny bitmap")
 
     def cf_import_sessions(self, sessions):
         """CF-recommender write path (examples/cf_recommender.c:36-47): every session is a sequence of item ids; all
