@@ -1,7 +1,7 @@
 // kernels/merge.hpp -- record emission for smatrix_merge / smatrix_import_csr (include/smatrix_batch.h): row tables, or a CSR,
 // straight into a bounded batch of packed {x, key, value} records -- the form the write path takes with in_stride == 3
 // (smatrix_apply_packed_dev).  No whole-matrix CSR and no triples of nnz words in between.
-// A fragment of smx_kernels.hpp: included there, after export.hpp, INSIDE namespace smx; not a header of its own.
+// A fragment of smx_kernels.hpp: included there, after export.hpp and rank_key.hpp, INSIDE namespace smx; not a header of its own.
 //
 // From row tables (one internal batch = the rows [r0, r1) of the export's row list, `items`, whose exact pair counts were scanned
 // into ptr[] by k_ex_count / k_ex_scan_*): the record of a row's j-th non-empty cell, in slot order, is number
@@ -81,24 +81,6 @@ struct MgScale {
     return val >= min_value && (key | val) != 0;
   }
   __device__ __forceinline__ const MgScale& at(uint32_t) const { return *this; }
-};
-
-// smatrix_merge_topk's filter: the pairs of row r whose rank key is at least thr[r] (k_mgt_select*, below), and the head pair.
-// mgt_key: larger is better -- by value, equal values by ascending column; unique within a row.
-__device__ __forceinline__ uint64_t mgt_key(uint32_t y, uint32_t v) { return ((uint64_t)v << 32) | (0xFFFFFFFFu - y); }
-
-struct MgTopkRow {
-  uint64_t thr;
-  uint32_t min_value;
-  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
-    if (val < min_value) return false;
-    return key == 0 ? val != 0 : mgt_key(key, val) >= thr;
-  }
-};
-struct MgTopk {
-  const uint64_t* thr;                                     // per row of the row list; 0 = every eligible pair
-  uint32_t min_value;
-  __device__ __forceinline__ MgTopkRow at(uint32_t r) const { return MgTopkRow{thr[r], min_value}; }
 };
 
 template <typename F>
@@ -324,21 +306,41 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
   }
 }
 
-// ---- the per-row selection of smatrix_merge_topk -------------------------------------------------------------------------------
-// thr[r] = the rank key of the m-th best ELIGIBLE pair of row r (y != 0, v >= min_value), or 0 when the row has at most m of them;
-// cnt[r] = the pairs the row keeps: min(m, eligible) + its head pair (y == 0) when v >= min_value.  MSB radix select on the 64-bit
-// key, 8 bits per pass, the 256 bins in LDS:
-//   pass 0      counts the eligible pairs and ORs their keys: a row of at most m is done, and the passes start at the highest
-//               byte that is not 0 in every key (small values: 3 passes less)
-//   a pass      re-reads the row (a wave-path row is at most 64 KiB and stays in L2) and counts, by their next byte, the keys
-//               that agree with the bytes chosen so far; the bins are walked from 255 down to the one that holds the key wanted
-//   the end     the last byte, or earlier when that bin holds ONE key: one more read of the row fetches it
-//   k_mgt_select       a wave per row of up to GETROW_WAVE_MAX cells (a histogram per wave: no workgroup barrier); longer rows are
-//                      noted in `big` (big[0] = entries, one row index each)
-//   k_mgt_select_big   those rows, ONE 1024-lane workgroup per row over all its segments -- they are few, and a histogram across
-//                      workgroups is not worth its launches
-// Both sum the non-empty cells they saw into *tot, as the k_mgx_count kernels do.  A cut row's seg_cnt entries are counted with
-// the finished threshold by k_mgt_emit_big<true>, batch by batch, as smatrix_merge does.
+// ---- smatrix_merge_topk / smatrix_merge_topk_by: the m best pairs of every row ------------------------------------------------------
+// thr[r] = the rank key of the m-th best ELIGIBLE pair of row r (y != 0, v >= min_value), or zero when the row has at most m of
+// them; cnt[r] = the pairs the row keeps: min(m, eligible) + its head pair (y == 0) when v >= min_value.  What a key is, is a
+// policy (kernels/rank_key.hpp for the bits, below for what a key is made from):
+//   MgtValueKey    {v, ~y}.  Free to make: the counting pass ORs the keys as it goes.
+//   MgtCosineKey   {the score's bits, ~y}.  The score of the pair (y, v) of row x is k_cf_neighbors' (kernels/rows.hpp), expression
+//                  for expression, in IEEE double:
+//                    tb = get(y, 0), 0 counted as 1;  den = sqrt(get(x, 0)) * sqrt(tb);  score = den != 0 && !(v > den) ? v / den : 0
+//                  A row without a head pair scores 0 everywhere and keeps its m lowest eligible columns; a dead cell scores 0.
+//                  The score is never stored per pair: every pass that needs it makes it again, each lane with its own
+//                  neighbour's get(y, 0) (apply_one<OP_GET>, as k_cf_neighbors: many independent look-ups in flight per wave).
+//                  So the counting pass makes no key, the row's own total is read only in a row that has more than m eligible
+//                  pairs, a pass of its own ORs the keys of such a row, and a row of at most 128 cells (a lane holds two) keeps
+//                  its two keys in registers: ONE gather per pair for the whole selection.
+// The selection of one row is an MSB radix select, 8 bits per pass, the 256 bins in LDS:
+//   the count   one read counts the eligible pairs: a row of at most m is done
+//   the start   from the OR of the keys (rank_key.hpp): the first digit worth a pass, the digits above it as the prefix
+//   a pass      re-reads the row (a wave-path row is at most 64 KiB and stays in L2) and counts, by their next digit, the keys
+//               that agree with the digits chosen so far; the bins are walked from 255 down to the one that holds the key wanted
+//   the end     the last digit, or earlier when that bin holds ONE key: one more read of the row fetches it
+//   k_mgt_select, k_mgc_select          mgt_select_row<P>, written once over the key policy: a wave per row of up to
+//                      GETROW_WAVE_MAX cells, a histogram per wave, fenced for the wave alone: no workgroup barrier.  Longer
+//                      rows are noted in `big` (big[0] = entries, one row index each).
+//   k_mgt_select_big, k_mgc_select_big  those rows, ONE 1024-lane workgroup per row over all its segments -- they are few, and a
+//                      histogram across workgroups is not worth its launches.  These two are still written out per key, with the
+//                      key arithmetic beside them (mgt_key, mgc_*): one body over the key policy, with or without a scope policy
+//                      under mgt_select_row, measured 4 to 9 % slower in k_mgt_select_big, the longest kernel of the value
+//                      selection, for a reason that was not found (profiles/merge_select_fold_time.txt).  What decides a branch
+//                      or a barrier in them comes out of LDS through readfirstlane: the same scalar in all 16 waves.
+// Both sum the non-empty cells they saw into *tot, as the k_mgx_count kernels do.  The emission is the walkers above with
+// MgRank<P>: the pair's key is made once more and compared with the row's threshold; zero = every eligible pair, and then
+// nothing is gathered.  A cut row's seg_cnt entries are counted with the finished threshold by k_*_emit_big<true>, batch by
+// batch, as smatrix_merge does.
+// Gathers per eligible pair of a row that the cosine rank cuts to m: 1 (the start) + the passes + 1 (a bin of one key) + 1
+// (emission; 2 in a row of two segments and more), or 1 + 1 in a row of at most 128 cells.
 __device__ __forceinline__ void mgt_wave_sync() {          // the LDS traffic of one wave, in program order for all its lanes
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -390,7 +392,229 @@ __device__ __forceinline__ void mgt_pick(const uint32_t* hist, uint32_t need, ui
   bucket = (uint32_t)__shfl((int)bk, src);
 }
 
+__device__ __forceinline__ uint64_t mgc_score_bits(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t y, uint32_t v) {
+  bool dummy = false;
+  uint32_t b_total = apply_one<OP_GET>(dir, dmask, arena, y, 0u, 0u, &dummy);
+  if (b_total == 0) b_total = 1;
+  const double num = (double)v;
+  const double den = sa * sqrt((double)b_total);
+  double score = 0.0;
+  if (den != 0.0 && !(num > den)) score = num / den;
+  return (uint64_t)__double_as_longlong(score);
+}
+
+// The key policies.  Beside the bits: FREE, a key costs no memory access; HOLD, a row that one step of a wave covers keeps its
+// keys in registers; Thr, the per-row thresholds in device memory; Src, what keys are made from, and Row, that for one row --
+// Src::row(x) for row id x, Src::at(r) for row r of the row list, Src::blank() before either: it makes no key yet.
+struct MgtValueKey : RkValue {
+  static constexpr bool FREE = true, HOLD = false;
+  struct Thr {
+    uint64_t* thr;
+    __device__ __forceinline__ Key load(uint32_t r) const { return thr[r]; }
+    __device__ __forceinline__ void store(uint32_t r, Key k) const { thr[r] = k; }
+  };
+  struct Row { __device__ __forceinline__ Key key(uint32_t y, uint32_t v) const { return make(y, v); } };
+  struct Src {
+    __device__ __forceinline__ Row blank() const { return Row{}; }
+    __device__ __forceinline__ Row row(uint32_t) const { return Row{}; }
+    __device__ __forceinline__ Row at(uint32_t) const { return Row{}; }
+  };
+};
+
+struct MgtCosineKey : RkCosine {
+  static constexpr bool FREE = false, HOLD = true;
+  struct Thr {
+    uint64_t* thr;                                         // the score half,
+    uint32_t* thr_col;                                     // the column half
+    __device__ __forceinline__ Key load(uint32_t r) const { return Key{thr[r], thr_col[r]}; }
+    __device__ __forceinline__ void store(uint32_t r, Key k) const { thr[r] = k.s; thr_col[r] = k.c; }
+  };
+  struct Row {
+    DirSlot* dir;
+    uint8_t* arena;
+    uint32_t dmask;
+    double sa;                                             // sqrt of the row's own total
+    __device__ __forceinline__ Key key(uint32_t y, uint32_t v) const { return make(y, mgc_score_bits(dir, dmask, arena, sa, y, v)); }
+  };
+  struct Src {
+    DirSlot* dir;
+    uint8_t* arena;
+    const uint64_t* items;                                 // the row list (the row's directory slot in the high word)
+    uint32_t dmask;
+    __device__ __forceinline__ Row blank() const { return Row{dir, arena, dmask, 0.0}; }
+    __device__ __forceinline__ Row row(uint32_t x) const {
+      bool dummy = false;
+      return Row{dir, arena, dmask, sqrt((double)apply_one<OP_GET>(dir, dmask, arena, x, 0u, 0u, &dummy))};
+    }
+    __device__ __forceinline__ Row at(uint32_t r) const { return row(dir[(uint32_t)(items[r] >> 32)].x); }
+  };
+};
+
+// the emission's filter: the pairs of row r whose rank key is at least the row's threshold, and the head pair
+template <typename P>
+struct MgRankRow {
+  typename P::Key thr;
+  typename P::Row row;
+  uint32_t min_value;
+  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
+    if (val < min_value) return false;
+    if (key == 0) return val != 0;
+    if (!P::FREE && P::is_zero(thr)) return true;
+    return P::ge(row.key(key, val), thr);
+  }
+};
+template <typename P>
+struct MgRank {
+  typename P::Thr thr;                                     // per row of the row list; zero = every eligible pair
+  typename P::Src src;
+  uint32_t min_value;
+  __device__ __forceinline__ MgRankRow<P> at(uint32_t r) const {
+    MgRankRow<P> f{thr.load(r), src.blank(), min_value};
+    if (P::FREE || !P::is_zero(f.thr)) f.row = src.at(r);   // (a row that keeps all its eligible pairs scores nothing)
+    return f;
+  }
+};
+using MgTopk = MgRank<MgtValueKey>;
+using MgCos = MgRank<MgtCosineKey>;
+
 __device__ __forceinline__ bool mgt_eligible(uint32_t key, uint32_t val, uint32_t min_value) { return key != 0 && val >= min_value; }
+
+template <typename K>
+struct MgtPair {                                           // the two cells a lane holds at one step, as rank keys
+  K k0, k1;
+  bool e0, e1;                                             // eligible
+};
+template <typename P>
+__device__ __forceinline__ MgtPair<typename P::Key> mgt_keys(const typename P::Row& row, uint32_t min_value, const uint4 q) {
+  MgtPair<typename P::Key> k{P::zero(), P::zero(), mgt_eligible(q.x, q.y, min_value), mgt_eligible(q.z, q.w, min_value)};
+  if (P::FREE || k.e0) k.k0 = row.key(q.x, q.y);
+  if (P::FREE || k.e1) k.k1 = row.key(q.z, q.w);
+  return k;
+}
+
+// A wave as "every lane" of a row's selection.  fetch: this lane's two cells of the 128 at p0 (every lane takes every step: the
+// steps hold ballots); or_words: over every lane, to every lane; hist_zero, pick: around a pass -- the bins emptied before
+// it, mgt_pick after it, the wave's LDS traffic fenced for the wave alone.
+struct MgtWave {
+  static constexpr uint32_t STEP = 128;
+  uint32_t* hist;                                          // this wave's 256 bins
+  uint32_t lane;
+  __device__ __forceinline__ uint4 fetch(const uint4* cells, uint32_t size, uint32_t p0) const {
+    const uint32_t p = p0 + 2 * lane;
+    return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
+  }
+  template <uint32_t N>
+  __device__ __forceinline__ void or_words(uint32_t (&w)[N]) const {
+#pragma unroll
+    for (uint32_t i = 0; i < N; i++) w[i] = mg_wave_or(w[i]);
+  }
+  __device__ __forceinline__ void hist_zero() const {
+    for (uint32_t i = lane; i < 256; i += 64) hist[i] = 0;
+    mgt_wave_sync();
+  }
+  __device__ __forceinline__ void pick(uint32_t need, uint32_t& d, uint32_t& above, uint32_t& bucket) const {
+    mgt_wave_sync();
+    mgt_pick<false>(hist, need, lane, d, above, bucket);
+    mgt_wave_sync();
+  }
+};
+
+// The selection of one row of up to GETROW_WAVE_MAX cells by a wave: -> the row's threshold, to every lane; elig and head as
+// cnt[] wants them; this lane's non-empty cells added to seen.
+template <typename P>
+__device__ __forceinline__ typename P::Key mgt_select_row(const MgtWave& sc, const typename P::Src& src, const uint4* cells, uint32_t size,
+                                                          uint32_t x, uint32_t m, uint32_t min_value, uint32_t& seen, uint32_t& elig,
+                                                          uint32_t& head) {
+  using S = MgtWave;
+  constexpr bool HOLD = P::HOLD;                           // (a row of one step keeps its keys in registers)
+  typename P::Row row = src.blank();
+  if (P::FREE) row = src.row(x);
+  typename P::Acc a = P::acc0();
+  uint4 q0 = make_uint4(0, 0, 0, 0);                       // the lane's first two cells: all of a row of one step
+  elig = 0; head = 0;
+  for (uint32_t p0 = 0; p0 < size; p0 += S::STEP) {
+    const uint4 q = sc.fetch(cells, size, p0);
+    if (HOLD && p0 == 0) q0 = q;
+    seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+    head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+    if (P::FREE) {
+      const MgtPair<typename P::Key> k = mgt_keys<P>(row, min_value, q);
+      if (k.e0) { elig++; P::acc_add(a, k.k0); }
+      if (k.e1) { elig++; P::acc_add(a, k.k1); }
+    } else {
+      elig += mgt_eligible(q.x, q.y, min_value) + mgt_eligible(q.z, q.w, min_value);
+    }
+  }
+  elig = mg_wave_sum(elig);
+  head = mg_wave_or(head);
+  if (elig <= m) return P::zero();
+  if (!P::FREE) row = src.row(x);
+  const bool held = HOLD && size <= S::STEP;
+  MgtPair<typename P::Key> k_held{P::zero(), P::zero(), false, false};
+  if (held) k_held = mgt_keys<P>(row, min_value, q0);
+  auto keys = [&](uint32_t p0) -> MgtPair<typename P::Key> { return held ? k_held : mgt_keys<P>(row, min_value, sc.fetch(cells, size, p0)); };
+  if (!P::FREE)
+    for (uint32_t p0 = 0; p0 < size; p0 += S::STEP) {
+      const MgtPair<typename P::Key> k = keys(p0);
+      if (k.e0) P::acc_add(a, k.k0);
+      if (k.e1) P::acc_add(a, k.k1);
+    }
+  sc.or_words(a.w);
+  typename P::Key prefix;
+  uint32_t dg = P::start(a, prefix), need = m;
+  for (;;) {
+    sc.hist_zero();
+    for (uint32_t p0 = 0; p0 < size; p0 += S::STEP) {
+      const MgtPair<typename P::Key> k = keys(p0);
+      mgt_hist_add(sc.hist, k.e0 && P::agrees_above(k.k0, prefix, dg), P::digit(k.k0, dg), sc.lane);
+      mgt_hist_add(sc.hist, k.e1 && P::agrees_above(k.k1, prefix, dg), P::digit(k.k1, dg), sc.lane);
+    }
+    uint32_t d, above, bucket;
+    sc.pick(need, d, above, bucket);
+    need -= above;
+    P::take_digit(prefix, dg, d);
+    if (dg == 0) return prefix;
+    if (bucket == 1) {                                     // the one key that agrees down to this digit
+      uint32_t w[P::W] = {};
+      for (uint32_t p0 = 0; p0 < size; p0 += S::STEP) {
+        const MgtPair<typename P::Key> k = keys(p0);
+        if (k.e0 && P::agrees_down(k.k0, prefix, dg)) P::or_words(w, k.k0);
+        if (k.e1 && P::agrees_down(k.k1, prefix, dg)) P::or_words(w, k.k1);
+      }
+      sc.or_words(w);
+      return P::from_words(w);
+    }
+    dg--;
+  }
+}
+
+// the rows of the row list, a wave each (the wave's number and the number of waves come from the kernel, as in mg_emit_rows)
+template <typename P>
+__device__ __forceinline__ void mgt_select_rows(const DirSlot* dir, uint8_t* arena, uint32_t n, const uint64_t* __restrict__ items,
+                                                uint32_t m, uint32_t min_value, const typename P::Src src, const typename P::Thr thr,
+                                                uint32_t* __restrict__ cnt, uint32_t* big, unsigned long long* tot, const uint32_t wave,
+                                                const uint32_t nwaves) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][256];
+  const MgtWave sc{s_hist[threadIdx.x >> 6], threadIdx.x & 63};
+  uint32_t seen = 0;
+  for (uint32_t r = wave; r < n; r += nwaves) {
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
+    if (size > GETROW_WAVE_MAX) {
+      if (sc.lane == 0) big[1 + atomicAdd(&big[0], 1u)] = r;
+      continue;
+    }
+    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
+    uint32_t elig, head;
+    const typename P::Key t = mgt_select_row<P>(sc, src, cells, size, s.y, m, min_value, seen, elig, head);
+    if (sc.lane == 0) { thr.store(r, t); cnt[r] = (elig < m ? elig : m) + head; }
+  }
+  seen = mg_wave_sum(seen);                                // (a wave's rows hold < 2^32 cells: rows * 8192 / waves)
+  if (sc.lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+}
+
+// ---- the workgroup-per-row selections, per key (see above) -----------------------------------------------------------------
+__device__ __forceinline__ uint64_t mgt_key(uint32_t y, uint32_t v) { return ((uint64_t)v << 32) | (0xFFFFFFFFu - y); }
 // (the shift is 56 at most; in two steps, so that 56 + 8 is no shift by 64)
 __device__ __forceinline__ bool mgt_agrees_above(uint64_t k, uint64_t prefix, uint32_t shift) { return (((k ^ prefix) >> shift) >> 8) == 0; }
 
@@ -400,72 +624,63 @@ __device__ __forceinline__ void mgt_fetch_key(const uint4 q, uint32_t min_value,
   if (mgt_eligible(q.x, q.y, min_value) && ((k0 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k0 >> 32); lo |= (uint32_t)k0; }
   if (mgt_eligible(q.z, q.w, min_value) && ((k1 ^ prefix) >> shift) == 0) { hi |= (uint32_t)(k1 >> 32); lo |= (uint32_t)k1; }
 }
+struct MgcPair {                                           // the two cells a lane holds at one step, as rank keys
+  uint64_t s0, s1;                                         // score bits
+  uint32_t c0, c1;                                         // 0xFFFFFFFF - y
+  bool e0, e1;                                             // eligible
+};
+
+__device__ __forceinline__ MgcPair mgc_keys(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t min_value, const uint4 q) {
+  MgcPair k{0, 0, ~q.x, ~q.z, mgt_eligible(q.x, q.y, min_value), mgt_eligible(q.z, q.w, min_value)};
+  if (k.e0) k.s0 = mgc_score_bits(dir, dmask, arena, sa, q.x, q.y);
+  if (k.e1) k.s1 = mgc_score_bits(dir, dmask, arena, sa, q.z, q.w);
+  return k;
+}
+
+// digit dg of the key: 11 .. 4 are the score's bytes 7 .. 0, 3 .. 0 the column key's
+__device__ __forceinline__ uint32_t mgc_digit(uint64_t s, uint32_t c, uint32_t dg) {
+  return dg >= 4 ? (uint32_t)(s >> (8 * (dg - 4))) & 255u : (c >> (8 * dg)) & 255u;
+}
+// the key agrees with the prefix in every digit above dg / down to dg (shifts in two steps: 56 + 8 is no shift by 64)
+__device__ __forceinline__ bool mgc_agrees_above(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
+  return dg >= 4 ? (((s ^ ps) >> (8 * (dg - 4))) >> 8) == 0 : s == ps && (((c ^ pc) >> (8 * dg)) >> 8) == 0;
+}
+__device__ __forceinline__ bool mgc_agrees_down(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
+  return dg >= 4 ? ((s ^ ps) >> (8 * (dg - 4))) == 0 : s == ps && ((c ^ pc) >> (8 * dg)) == 0;
+}
+// where the passes start, from the OR and the AND of two keys and more: the highest digit in which they differ (keys are
+// unique: there is one), and the digits above it -- common to all keys -- as the prefix
+__device__ __forceinline__ void mgc_start(uint64_t or_s, uint64_t and_s, uint32_t or_c, uint32_t and_c, uint32_t& dg, uint64_t& ps, uint32_t& pc) {
+  const uint64_t ds = or_s ^ and_s;
+  const uint32_t dc = or_c ^ and_c;
+  if (ds) {
+    const uint32_t sh = (63u - (uint32_t)__clzll((long long)ds)) & ~7u;
+    dg = 4 + (sh >> 3);
+    ps = ((and_s >> sh) >> 8) << 8 << sh;
+    pc = 0;
+  } else {
+    const uint32_t sh = dc ? (31u - (uint32_t)__clz((int)dc)) & ~7u : 0u;
+    dg = sh >> 3;
+    ps = and_s;
+    pc = ((and_c >> sh) >> 8) << 8 << sh;
+  }
+}
+__device__ __forceinline__ void mgc_take_digit(uint64_t& ps, uint32_t& pc, uint32_t dg, uint32_t d) {
+  if (dg >= 4) ps |= (uint64_t)d << (8 * (dg - 4));
+  else pc |= d << (8 * dg);
+}
+
+__device__ __forceinline__ uint32_t mg_wave_and(uint32_t v) {
+  for (uint32_t d = 32; d; d >>= 1) v &= (uint32_t)__shfl_xor((int)v, d);
+  return v;
+}
 
 __global__ __launch_bounds__(256) void k_mgt_select(const DirSlot* __restrict__ dir, uint8_t* arena, uint32_t n,
                                                     const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value,
                                                     uint64_t* __restrict__ thr, uint32_t* __restrict__ cnt, uint32_t* big,
                                                     unsigned long long* tot) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][256];
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t* hist = s_hist[threadIdx.x >> 6];
-  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-  uint32_t seen = 0;
-  for (uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n; r += nwaves) {
-    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
-    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
-    if (size > GETROW_WAVE_MAX) {
-      if (lane == 0) big[1 + atomicAdd(&big[0], 1u)] = r;
-      continue;
-    }
-    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
-    auto fetch = [&](uint32_t p0) -> uint4 {               // (every lane takes every step: the steps hold ballots)
-      const uint32_t p = p0 + 2 * lane;
-      return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
-    };
-    uint32_t elig = 0, head = 0, or_hi = 0, or_lo = 0;
-    for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-      const uint4 q = fetch(p0);
-      seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
-      head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
-      if (mgt_eligible(q.x, q.y, min_value)) { elig++; or_hi |= q.y; or_lo |= ~q.x; }
-      if (mgt_eligible(q.z, q.w, min_value)) { elig++; or_hi |= q.w; or_lo |= ~q.z; }
-    }
-    elig = mg_wave_sum(elig);
-    head = mg_wave_or(head);
-    uint64_t t = 0;
-    if (elig > m) {
-      const uint64_t orall = ((uint64_t)mg_wave_or(or_hi) << 32) | mg_wave_or(or_lo);   // (two keys and more: not 0)
-      uint32_t shift = (63u - (uint32_t)__clzll((long long)orall)) & ~7u, need = m;
-      uint64_t prefix = 0;
-      for (;;) {
-        for (uint32_t i = lane; i < 256; i += 64) hist[i] = 0;
-        mgt_wave_sync();
-        for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-          const uint4 q = fetch(p0);
-          const uint64_t k0 = mgt_key(q.x, q.y), k1 = mgt_key(q.z, q.w);
-          mgt_hist_add(hist, mgt_eligible(q.x, q.y, min_value) && mgt_agrees_above(k0, prefix, shift), (uint32_t)(k0 >> shift) & 255u, lane);
-          mgt_hist_add(hist, mgt_eligible(q.z, q.w, min_value) && mgt_agrees_above(k1, prefix, shift), (uint32_t)(k1 >> shift) & 255u, lane);
-        }
-        mgt_wave_sync();
-        uint32_t d, above, bucket;
-        mgt_pick<false>(hist, need, lane, d, above, bucket);
-        mgt_wave_sync();
-        need -= above;
-        prefix |= (uint64_t)d << shift;
-        if (shift == 0) { t = prefix; break; }
-        if (bucket == 1) {                                 // the one key that agrees down to this byte
-          uint32_t hi = 0, lo = 0;
-          for (uint32_t p0 = 0; p0 < size; p0 += 128) mgt_fetch_key(fetch(p0), min_value, prefix, shift, hi, lo);
-          t = ((uint64_t)mg_wave_or(hi) << 32) | mg_wave_or(lo);
-          break;
-        }
-        shift -= 8;
-      }
-    }
-    if (lane == 0) { thr[r] = t; cnt[r] = (elig < m ? elig : m) + head; }
-  }
-  seen = mg_wave_sum(seen);
-  if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+  mgt_select_rows<MgtValueKey>(dir, arena, n, items, m, min_value, {}, {thr}, cnt, big, tot,
+                               (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
 }
 
 __global__ __launch_bounds__(1024) void k_mgt_select_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
@@ -544,219 +759,12 @@ __global__ __launch_bounds__(1024) void k_mgt_select_big(const DirSlot* __restri
   }
 }
 
-// the emission of smatrix_merge_topk: the walkers above with the per-row threshold
-__global__ __launch_bounds__(256) void k_mgt_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
-                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
-                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgTopk f) {
-  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, f);
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(1024) void k_mgt_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
-                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
-                                                       const uint32_t* big, uint32_t* seg_cnt, const MgTopk f) {
-  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
-}
-
-// ---- smatrix_merge_topk_by, SMATRIX_RANK_COSINE: the m pairs of every row that SCORE best ------------------------------------
-// The score of the pair (y, v) of row x is k_cf_neighbors' (kernels/rows.hpp), expression for expression, in IEEE double:
-//   tb = get(y, 0), 0 counted as 1;  den = sqrt(get(x, 0)) * sqrt(tb);  score = den != 0 && !(v > den) ? v / den : 0
-// and the rank key is 96 bits, {the score's bit pattern, 0xFFFFFFFF - y}: larger is better -- by score (scores are >= 0: their
-// patterns order as they do), equal scores by ascending column; unique within a row.  A row without a head pair scores 0
-// everywhere and keeps its m lowest eligible columns; a dead cell scores 0.
-// The score is never stored per pair: every pass that needs it makes it again, each lane with its own neighbour's get(y, 0)
-// (apply_one<OP_GET>, as k_cf_neighbors: many independent look-ups in flight per wave).  The row's own total is read once per
-// row, and only in a row that has more than m eligible pairs.
-//   k_mgc_select       a wave per row of up to GETROW_WAVE_MAX cells.  One read counts the eligible pairs: a row of at most m is
-//                      done.  Otherwise a scoring pass ORs and ANDs the keys -- positive doubles share their top bytes, so the
-//                      passes start at the highest byte in which the row's keys DIFFER, with the bytes above it as the prefix --
-//                      and the MSB radix select of k_mgt_select runs over the 12 bytes, the 8 of the score and then the 4 of the
-//                      column; a bin of one key ends it.  A row of at most 128 cells (a lane holds two) keeps its two keys in
-//                      registers: ONE gather per pair for the whole selection.
-//   k_mgc_select_big   the longer rows, one 1024-lane workgroup per row over all its segments
-//   k_mgc_emit, k_mgc_emit_big<C>   the walkers with MgCos: the pair's score is made once more and compared with the row's
-//                      threshold {thr[r], thr_col[r]}; all zero = every eligible pair, and then nothing is gathered
-// Gathers per eligible pair of a row that is cut to m: 1 (OR / AND) + the passes + 1 (a bin of one key) + 1 (emission; 2 in a
-// row of two segments and more), or 1 + 1 in a row of at most 128 cells.
-struct MgcPair {                                           // the two cells a lane holds at one step, as rank keys
-  uint64_t s0, s1;                                         // score bits
-  uint32_t c0, c1;                                         // 0xFFFFFFFF - y
-  bool e0, e1;                                             // eligible
-};
-
-__device__ __forceinline__ uint64_t mgc_score_bits(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t y, uint32_t v) {
-  bool dummy = false;
-  uint32_t b_total = apply_one<OP_GET>(dir, dmask, arena, y, 0u, 0u, &dummy);
-  if (b_total == 0) b_total = 1;
-  const double num = (double)v;
-  const double den = sa * sqrt((double)b_total);
-  double score = 0.0;
-  if (den != 0.0 && !(num > den)) score = num / den;
-  return (uint64_t)__double_as_longlong(score);
-}
-
-__device__ __forceinline__ MgcPair mgc_keys(DirSlot* dir, uint32_t dmask, uint8_t* arena, double sa, uint32_t min_value, const uint4 q) {
-  MgcPair k{0, 0, ~q.x, ~q.z, mgt_eligible(q.x, q.y, min_value), mgt_eligible(q.z, q.w, min_value)};
-  if (k.e0) k.s0 = mgc_score_bits(dir, dmask, arena, sa, q.x, q.y);
-  if (k.e1) k.s1 = mgc_score_bits(dir, dmask, arena, sa, q.z, q.w);
-  return k;
-}
-
-// digit dg of the key: 11 .. 4 are the score's bytes 7 .. 0, 3 .. 0 the column key's
-__device__ __forceinline__ uint32_t mgc_digit(uint64_t s, uint32_t c, uint32_t dg) {
-  return dg >= 4 ? (uint32_t)(s >> (8 * (dg - 4))) & 255u : (c >> (8 * dg)) & 255u;
-}
-// the key agrees with the prefix in every digit above dg / down to dg (shifts in two steps: 56 + 8 is no shift by 64)
-__device__ __forceinline__ bool mgc_agrees_above(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
-  return dg >= 4 ? (((s ^ ps) >> (8 * (dg - 4))) >> 8) == 0 : s == ps && (((c ^ pc) >> (8 * dg)) >> 8) == 0;
-}
-__device__ __forceinline__ bool mgc_agrees_down(uint64_t s, uint32_t c, uint64_t ps, uint32_t pc, uint32_t dg) {
-  return dg >= 4 ? ((s ^ ps) >> (8 * (dg - 4))) == 0 : s == ps && ((c ^ pc) >> (8 * dg)) == 0;
-}
-// where the passes start, from the OR and the AND of two keys and more: the highest digit in which they differ (keys are
-// unique: there is one), and the digits above it -- common to all keys -- as the prefix
-__device__ __forceinline__ void mgc_start(uint64_t or_s, uint64_t and_s, uint32_t or_c, uint32_t and_c, uint32_t& dg, uint64_t& ps, uint32_t& pc) {
-  const uint64_t ds = or_s ^ and_s;
-  const uint32_t dc = or_c ^ and_c;
-  if (ds) {
-    const uint32_t sh = (63u - (uint32_t)__clzll((long long)ds)) & ~7u;
-    dg = 4 + (sh >> 3);
-    ps = ((and_s >> sh) >> 8) << 8 << sh;
-    pc = 0;
-  } else {
-    const uint32_t sh = dc ? (31u - (uint32_t)__clz((int)dc)) & ~7u : 0u;
-    dg = sh >> 3;
-    ps = and_s;
-    pc = ((and_c >> sh) >> 8) << 8 << sh;
-  }
-}
-__device__ __forceinline__ void mgc_take_digit(uint64_t& ps, uint32_t& pc, uint32_t dg, uint32_t d) {
-  if (dg >= 4) ps |= (uint64_t)d << (8 * (dg - 4));
-  else pc |= d << (8 * dg);
-}
-
-__device__ __forceinline__ uint32_t mg_wave_and(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v &= (uint32_t)__shfl_xor((int)v, d);
-  return v;
-}
-
-struct MgCosRow {
-  uint64_t thr;
-  uint32_t thr_col, min_value, dmask;
-  double sa;                                               // sqrt of the row's own total
-  DirSlot* dir;
-  uint8_t* arena;
-  __device__ __forceinline__ bool operator()(uint32_t key, uint32_t& val) const {
-    if (val < min_value) return false;
-    if (key == 0) return val != 0;
-    if ((thr | thr_col) == 0) return true;
-    const uint64_t s = mgc_score_bits(dir, dmask, arena, sa, key, val);
-    return s > thr || (s == thr && ~key >= thr_col);
-  }
-};
-struct MgCos {
-  const uint64_t* thr;                                     // per row of the row list: the score bits of the m-th best key,
-  const uint32_t* thr_col;                                 // and its column half; both 0 = every eligible pair
-  const uint64_t* items;                                   // the row list (the row's directory slot in the high word)
-  DirSlot* dir;
-  uint8_t* arena;
-  uint32_t dmask, min_value;
-  __device__ __forceinline__ MgCosRow at(uint32_t r) const {
-    MgCosRow f{thr[r], thr_col[r], min_value, dmask, 0.0, dir, arena};
-    if (f.thr | f.thr_col) {                               // (a row that keeps all its eligible pairs scores nothing)
-      bool dummy = false;
-      f.sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, dir[(uint32_t)(items[r] >> 32)].x, 0u, 0u, &dummy));
-    }
-    return f;
-  }
-};
-
 __global__ __launch_bounds__(256) void k_mgc_select(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t n,
                                                     const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value,
                                                     uint64_t* __restrict__ thr, uint32_t* __restrict__ thr_col,
                                                     uint32_t* __restrict__ cnt, uint32_t* big, unsigned long long* tot) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][256];
-  const uint32_t lane = threadIdx.x & 63;
-  uint32_t* hist = s_hist[threadIdx.x >> 6];
-  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-  uint32_t seen = 0;
-  for (uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n; r += nwaves) {
-    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
-    const uint32_t size = s.z ? 1u << meta_lg(s.x) : 0u;
-    if (size > GETROW_WAVE_MAX) {
-      if (lane == 0) big[1 + atomicAdd(&big[0], 1u)] = r;
-      continue;
-    }
-    const uint4* cells = s.z ? reinterpret_cast<const uint4*>(row_cells(arena, s.z)) : nullptr;
-    auto fetch = [&](uint32_t p0) -> uint4 {               // (every lane takes every step: the steps hold ballots)
-      const uint32_t p = p0 + 2 * lane;
-      return p < size ? cells[p >> 1] : make_uint4(0, 0, 0, 0);
-    };
-    uint32_t elig = 0, head = 0;
-    uint4 q0 = make_uint4(0, 0, 0, 0);                     // the lane's first two cells: all of a row of at most 128
-    for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-      const uint4 q = fetch(p0);
-      if (p0 == 0) q0 = q;
-      seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
-      head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
-      elig += mgt_eligible(q.x, q.y, min_value) + mgt_eligible(q.z, q.w, min_value);
-    }
-    elig = mg_wave_sum(elig);
-    head = mg_wave_or(head);
-    uint64_t ts = 0;
-    uint32_t tc = 0;
-    if (elig > m) {
-      bool dummy = false;
-      const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, s.y, 0u, 0u, &dummy));
-      const bool small = size <= 128;
-      MgcPair held{0, 0, 0, 0, false, false};
-      if (small) held = mgc_keys(dir, dmask, arena, sa, min_value, q0);
-      auto load = [&](uint32_t p0) -> MgcPair { return small ? held : mgc_keys(dir, dmask, arena, sa, min_value, fetch(p0)); };
-      uint32_t or_h = 0, or_l = 0, or_c = 0, and_h = ~0u, and_l = ~0u, and_c = ~0u;
-      for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-        const MgcPair k = load(p0);
-        if (k.e0) { or_h |= (uint32_t)(k.s0 >> 32); or_l |= (uint32_t)k.s0; or_c |= k.c0; and_h &= (uint32_t)(k.s0 >> 32); and_l &= (uint32_t)k.s0; and_c &= k.c0; }
-        if (k.e1) { or_h |= (uint32_t)(k.s1 >> 32); or_l |= (uint32_t)k.s1; or_c |= k.c1; and_h &= (uint32_t)(k.s1 >> 32); and_l &= (uint32_t)k.s1; and_c &= k.c1; }
-      }
-      uint32_t dg, need = m;
-      uint64_t ps;
-      uint32_t pc;
-      mgc_start(((uint64_t)mg_wave_or(or_h) << 32) | mg_wave_or(or_l), ((uint64_t)mg_wave_and(and_h) << 32) | mg_wave_and(and_l),
-                mg_wave_or(or_c), mg_wave_and(and_c), dg, ps, pc);
-      for (;;) {
-        for (uint32_t i = lane; i < 256; i += 64) hist[i] = 0;
-        mgt_wave_sync();
-        for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-          const MgcPair k = load(p0);
-          mgt_hist_add(hist, k.e0 && mgc_agrees_above(k.s0, k.c0, ps, pc, dg), mgc_digit(k.s0, k.c0, dg), lane);
-          mgt_hist_add(hist, k.e1 && mgc_agrees_above(k.s1, k.c1, ps, pc, dg), mgc_digit(k.s1, k.c1, dg), lane);
-        }
-        mgt_wave_sync();
-        uint32_t d, above, bucket;
-        mgt_pick<false>(hist, need, lane, d, above, bucket);
-        mgt_wave_sync();
-        need -= above;
-        mgc_take_digit(ps, pc, dg, d);
-        if (dg == 0) break;
-        if (bucket == 1) {                                 // the one key that agrees down to this digit
-          uint32_t hi = 0, lo = 0, col = 0;
-          for (uint32_t p0 = 0; p0 < size; p0 += 128) {
-            const MgcPair k = load(p0);
-            if (k.e0 && mgc_agrees_down(k.s0, k.c0, ps, pc, dg)) { hi |= (uint32_t)(k.s0 >> 32); lo |= (uint32_t)k.s0; col |= k.c0; }
-            if (k.e1 && mgc_agrees_down(k.s1, k.c1, ps, pc, dg)) { hi |= (uint32_t)(k.s1 >> 32); lo |= (uint32_t)k.s1; col |= k.c1; }
-          }
-          ps = ((uint64_t)mg_wave_or(hi) << 32) | mg_wave_or(lo);
-          pc = mg_wave_or(col);
-          break;
-        }
-        dg--;
-      }
-      ts = ps; tc = pc;
-    }
-    if (lane == 0) { thr[r] = ts; thr_col[r] = tc; cnt[r] = (elig < m ? elig : m) + head; }
-  }
-  seen = mg_wave_sum(seen);
-  if (lane == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+  mgt_select_rows<MgtCosineKey>(dir, arena, n, items, m, min_value, {dir, arena, items, dmask}, {thr, thr_col}, cnt, big, tot,
+                                (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
 }
 
 __global__ __launch_bounds__(1024) void k_mgc_select_big(DirSlot* dir, uint32_t dmask, uint8_t* arena, const uint64_t* __restrict__ items,
@@ -855,6 +863,20 @@ __global__ __launch_bounds__(1024) void k_mgc_select_big(DirSlot* dir, uint32_t 
     if (threadIdx.x == 0) { thr[r] = ts; thr_col[r] = tc; cnt[r] = (elig < m ? elig : m) + head; }
     __syncthreads();                                                   // (wacc and acc are the next row's)
   }
+}
+
+// the emission: the walkers above with the per-row threshold
+__global__ __launch_bounds__(256) void k_mgt_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgTopk f) {
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6, f);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mgt_emit_big(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                       const uint32_t* big, uint32_t* seg_cnt, const MgTopk f) {
+  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
 }
 
 __global__ __launch_bounds__(256) void k_mgc_emit(const DirSlot* __restrict__ dir, uint8_t* arena, const uint64_t* __restrict__ items,

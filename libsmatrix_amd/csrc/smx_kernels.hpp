@@ -32,6 +32,7 @@ namespace smx {
 #include "kernels/growth.hpp"
 #include "kernels/rows.hpp"
 #include "kernels/export.hpp"
+#include "kernels/rank_key.hpp"
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
 #include "kernels/io_router.hpp"

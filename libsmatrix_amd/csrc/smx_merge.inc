@@ -19,10 +19,10 @@
 // the source 8 (row list) + 4 (counts) + 8 (scan) bytes -- nothing per pair.
 // merge_scaled: merge with the counts of the SURVIVORS of its transform (k_mgx_count*, instead of the export's k_ex_count*) under
 //        the same scan, so the cuts and the rows' record offsets are those of what k_mgx_emit* will write; same memory.
-// merge_topk: the same with the counts and an 8-byte threshold per row from the selection (k_mgt_select*); the emission filters
-//        by that threshold (k_mgt_emit*) and counts a cut row's segments batch by batch, as merge does.  28 bytes per row.
-// merge_topk_by, SMATRIX_RANK_COSINE: merge_topk with the selection and the emission of the cosine rank (k_mgc_*): the threshold
-//        is 12 bytes per row, its score half in thr and its column half in thr_col.  32 bytes per row, no score per pair.
+// merge_topk, merge_topk_by: the same with the counts and a threshold per row from the selection (mg_count_selected); the emission
+//        filters by that threshold and counts a cut row's segments batch by batch, as merge does.  By value (k_mgt_*) the threshold
+//        is 8 bytes, 28 bytes per row; by cosine (k_mgc_*) 12, its score half in thr and its column half in thr_col, 32 bytes per
+//        row and no score per pair.
 
 namespace {
 
@@ -282,6 +282,36 @@ void mg_count_filtered(MergeCall& c, bool scan_timed, Launch launch, Report repo
   }
 }
 
+// The count stage of the top-k flavours: the selection, which leaves every row's threshold and, with it, the number of pairs the
+// row keeps -- the count of an uncut row needs no pass of its own.  `big` lists the rows of more than GETROW_WAVE_MAX cells here
+// (one word each: it has room for two per 128 KiB of row tables, and such a row is 128 KiB at least); the emission of every batch
+// starts it afresh.  launch(c, kernel, grid, lanes, n...) is the flavour's argument list, for the wave-per-row kernel (n = the
+// rows) and for the workgroup-per-row kernel (no n); col_half: the thresholds have a column half, in thr_col.
+template <typename KW, typename KB, typename Launch>
+auto mg_count_selected(const char* flavour, bool col_half, KW k_wave, KB k_big, Launch launch) {
+  return [=](MergeCall& c) {
+    mg_count_filtered(c, true,
+      [&] {
+        c.g.thr.need(c.n);
+        if (col_half) c.g.thr_col.need(c.n);
+        launch(c, k_wave, dim3(mg_row_grid(c.n)), dim3(256), (uint32_t)c.n);
+        launch(c, k_big, dim3(c.big_grid), dim3(1024));
+      },
+      [&](float sel, float cnt) {
+        fprintf(stderr, "[smatrix] %s: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
+                flavour, sel, cnt, (unsigned long long)c.kept, c.seen);
+      });
+  };
+}
+
+// their emit stage: the rows, then the segments of the cut rows counted and written, all with the flavour's filter
+template <typename K, typename KC, typename KB, typename F>
+void mg_emit_topk(const MergeCall& c, K k_rows, KC k_big_count, KB k_big, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e, const F f) {
+  mg_emit(c, k_rows, r0, r1, rec, e, f);
+  mg_emit_big(c, k_big_count, r0, rec, e, f);
+  mg_emit_big(c, k_big, r0, rec, e, f);
+}
+
 }  // namespace
 
 extern "C" {
@@ -327,28 +357,12 @@ int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint3
                        uint64_t* n_dropped) {
   if (m == 0) return -1;
   return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
-    [&](MergeCall& c) {
-      // the selection: every row's threshold and, with it, the number of pairs the row keeps -- the count of an uncut row needs
-      // no pass of its own.  `big` lists the rows of more than GETROW_WAVE_MAX cells here (one word each: it has room for two per
-      // 128 KiB of row tables, and such a row is 128 KiB at least); the emission of every batch starts it afresh.
-      mg_count_filtered(c, true,
-        [&] {
-          c.g.thr.need(c.n);
-          hipLaunchKernelGGL(k_mgt_select, dim3(mg_row_grid(c.n)), dim3(256), 0, c.s, c.sm->d_dir, c.sm->arena.base, (uint32_t)c.n,
-                             c.x.items.p, m, min_value, c.g.thr.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
-          hipLaunchKernelGGL(k_mgt_select_big, dim3(c.big_grid), dim3(1024), 0, c.s, c.sm->d_dir, c.sm->arena.base, c.x.items.p, m,
-                             min_value, c.g.thr.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
-        },
-        [&](float sel, float cnt) {
-          fprintf(stderr, "[smatrix] merge_topk: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
-                  sel, cnt, (unsigned long long)c.kept, c.seen);
-        });
-    },
+    mg_count_selected("merge_topk", false, k_mgt_select, k_mgt_select_big, [=](MergeCall& c, auto kernel, dim3 grid, dim3 lanes, auto... n) {
+      hipLaunchKernelGGL(kernel, grid, lanes, 0, c.s, c.sm->d_dir, c.sm->arena.base, n..., c.x.items.p, m, min_value, c.g.thr.p,
+                         c.x.cnt.p, c.g.big.p, c.g.tot.p);
+    }),
     [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
-      const MgTopk f{c.g.thr.p, min_value};
-      mg_emit(c, k_mgt_emit, r0, r1, rec, e, f);
-      mg_emit_big(c, k_mgt_emit_big<true>, r0, rec, e, f);
-      mg_emit_big(c, k_mgt_emit_big<false>, r0, rec, e, f);
+      mg_emit_topk(c, k_mgt_emit, k_mgt_emit_big<true>, k_mgt_emit_big<false>, r0, r1, rec, e, MgTopk{{c.g.thr.p}, {}, min_value});
     });
 }
 
@@ -357,27 +371,13 @@ int smatrix_merge_topk_by(smatrix_t* dst, smatrix_t* src, int op, int rank, uint
   if (rank == SMATRIX_RANK_VALUE) return smatrix_merge_topk(dst, src, op, m, min_value, max_batch, n_ops, n_dropped);
   if (rank != SMATRIX_RANK_COSINE || m == 0) return -1;
   return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
-    [&](MergeCall& c) {
-      // merge_topk's count stage with the cosine selection: the kept counts in x.cnt, the thresholds in thr and thr_col
-      mg_count_filtered(c, true,
-        [&] {
-          c.g.thr.need(c.n);
-          c.g.thr_col.need(c.n);
-          hipLaunchKernelGGL(k_mgc_select, dim3(mg_row_grid(c.n)), dim3(256), 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base,
-                             (uint32_t)c.n, c.x.items.p, m, min_value, c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
-          hipLaunchKernelGGL(k_mgc_select_big, dim3(c.big_grid), dim3(1024), 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base,
-                             c.x.items.p, m, min_value, c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
-        },
-        [&](float sel, float cnt) {
-          fprintf(stderr, "[smatrix] merge_topk_by cosine: selection %.3f ms (the kept count of every row with it), count scan %.3f ms, %llu of %llu pairs survive\n",
-                  sel, cnt, (unsigned long long)c.kept, c.seen);
-        });
-    },
+    mg_count_selected("merge_topk_by cosine", true, k_mgc_select, k_mgc_select_big, [=](MergeCall& c, auto kernel, dim3 grid, dim3 lanes, auto... n) {
+      hipLaunchKernelGGL(kernel, grid, lanes, 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base, n..., c.x.items.p, m, min_value,
+                         c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+    }),
     [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
-      const MgCos f{c.g.thr.p, c.g.thr_col.p, c.x.items.p, c.sm->d_dir, c.sm->arena.base, c.sm->dir_size - 1, min_value};
-      mg_emit(c, k_mgc_emit, r0, r1, rec, e, f);
-      mg_emit_big(c, k_mgc_emit_big<true>, r0, rec, e, f);
-      mg_emit_big(c, k_mgc_emit_big<false>, r0, rec, e, f);
+      mg_emit_topk(c, k_mgc_emit, k_mgc_emit_big<true>, k_mgc_emit_big<false>, r0, r1, rec, e,
+                   MgCos{{c.g.thr.p, c.g.thr_col.p}, {c.sm->d_dir, c.sm->arena.base, c.x.items.p, c.sm->dir_size - 1}, min_value});
     });
 }
 

@@ -1,14 +1,17 @@
-"""What tests/test_gpu_merge.py, test_gpu_merge_scaled.py and test_gpu_merge_topk.py share (a plain module, no tests of its own):
-the op codes, the expected ops of a merge read from an oracle, the comparison of a matrix with its oracle, the source builders.
+"""What tests/test_gpu_merge.py, test_gpu_merge_scaled.py, test_gpu_merge_topk.py and test_gpu_merge_topk_by.py share (a plain
+module, no tests of its own): the op codes, the expected ops of a merge read from an oracle, the comparison of a matrix with its
+oracle, the source builders, and of the two top-k files the row shapes and the case of the rows around one step of a wave.
 
 A SIDE of a comparison is an oracle or a candidate list -- the triple (x, y, v) that ops_of() makes of one."""
 import numpy as np
 import pytest
 
+from libsmatrix_amd import SparseMatrix
 from libsmatrix_amd.stream import Stream
 
 GET, SET, INCR, DECR = 0, 1, 2, 3
 OPS = {"set": SET, "incr": INCR, "decr": DECR}
+M_MAX = 0xFFFFFFFF
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -92,6 +95,16 @@ def both(m, o, op, x, y, v):
     o.apply(op, x, y, v)
 
 
+def row_dict(m, x):
+    """the non-empty slots of row x as {column: value} (getRowLength is not the pair count in a row with a column-0 pair: Q1)"""
+    kv = m.row_slots(x)
+    return {int(k): int(v) for k, v in kv[(kv[:, 0] != 0) | (kv[:, 1] != 0)]}
+
+
+def one_row(m, o, x, ys, vs):
+    both(m, o, SET, np.full(len(ys), x, np.uint32), np.asarray(ys, np.uint32), np.asarray(vs, np.uint32))
+
+
 def assert_export_equal(a, b, tag=""):
     for k, (u, v) in enumerate(zip(a, b)):
         assert u.shape == v.shape, (tag, k, u.shape, v.shape)
@@ -140,3 +153,39 @@ def src_one_long_row(m, o, golden, small=False, additions=None):
     both(m, o, INCR, xs, rng.integers(1, 1 << 32, xs.size, dtype=np.uint32), rng.integers(1, 9, xs.size, dtype=np.uint32))
     if additions:
         additions(m, o)
+
+
+# ---- the top-k merges: the row shapes of their `regimes` fixtures, and the case both files run on the rows around one step ------
+# keys -> table: a table holds at most size / 2 keys, so these counts give 16, 512, 8192 (the wave path's last), 16384 and 32768
+# (one workgroup, one segment), 65536 and 131072 slots (2 and 4 segments: cut rows).
+REGIMES = {10: (7, 16), 11: (200, 512), 12: (3000, 8192), 13: (6000, 16384), 14: (12000, 32768), 15: (20000, 65536), 16: (40000, 131072)}
+# A wave holds 128 cells at one step, and a rank whose keys cost a gather keeps those of such a row in registers: rows of 64 and 128
+# slots on that path, 256 on the other.  Rows 20 and 22 have a head pair, 21 has none.
+ONE_STEP = {20: (30, 64), 21: (60, 128), 22: (120, 256)}
+ONE_STEP_HEADS = {20: 40, 22: 300}
+
+
+def check_rows_around_one_step(oracle_mod, merged, column_totals):
+    """merged = the file's merged_topk / merged_cos.  Values 1..5: ties everywhere; with column_totals the columns come from a pool
+    of 400 ids of which 300 have a row with a head total in 1..50 (as the cosine file's regimes).  m = 1, half of and one less than
+    every row's eligible count."""
+    rng = np.random.default_rng(128)
+    src, o_src = SparseMatrix(), oracle_mod.Oracle()
+    pool = (50000 + rng.permutation(400)).astype(np.uint32)
+    if column_totals:
+        both(src, o_src, SET, pool[:300], np.zeros(300, np.uint32), rng.integers(1, 51, 300).astype(np.uint32))
+    for x, (n, size) in ONE_STEP.items():
+        one_row(src, o_src, x, rng.permutation(pool)[:n], rng.integers(1, 6, n))
+        assert src.row_info(x) == o_src.row_info(x) and o_src.row_info(x)[0] == size, (x, src.row_info(x), o_src.row_info(x))
+    both(src, o_src, SET, u32(*ONE_STEP_HEADS), np.zeros(len(ONE_STEP_HEADS), np.uint32), u32(*ONE_STEP_HEADS.values()))
+    for x, (n, size) in ONE_STEP.items():                                 # the sizes of the source as it is merged
+        assert src.row_info(x) == o_src.row_info(x) and o_src.row_info(x)[0] == size, (x, src.row_info(x), o_src.row_info(x))
+    cand = ops_of(o_src)
+    for m in sorted({k for n, _ in ONE_STEP.values() for k in (1, n // 2, n - 1)}):
+        dst, o_dst = SparseMatrix(), oracle_mod.Oracle()
+        ops, _ = merged(dst, o_dst, src, cand, "set", m, 1, tag="one step m %d" % m)
+        for x, (n, size) in ONE_STEP.items():                             # (every pair is eligible: v >= 1)
+            assert int(np.count_nonzero((ops[0] == x) & (ops[1] != 0))) == min(m, n), (x, m)
+            assert len(row_dict(dst, x)) == min(m, n) + (x in ONE_STEP_HEADS), (x, m)
+        dst.close(); o_dst.close()
+    src.close(); o_src.close()

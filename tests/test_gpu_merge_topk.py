@@ -13,11 +13,10 @@ import numpy as np
 import pytest
 
 from libsmatrix_amd import SparseMatrix
-from tests.merge_helpers import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, device, ops_of, u32)  # noqa: F401
+from tests.merge_helpers import (DECR, GET, INCR, M_MAX, OPS, REGIMES, SET, assert_export_equal, both, check,  # noqa: F401
+                                 check_rows_around_one_step, device, one_row, ops_of, row_dict, u32)
 
 pytestmark = pytest.mark.gpu
-
-M_MAX = 0xFFFFFFFF
 
 
 def topk(cand, m, min_value):
@@ -45,20 +44,8 @@ def merged_topk(dst, o_dst, src, cand, op, m, min_value, max_batch=0, tag=""):
     return ops, d
 
 
-def row_dict(m, x):
-    """the non-empty slots of row x as {column: value} (getRowLength is not the pair count in a row with a column-0 pair: Q1)"""
-    kv = m.row_slots(x)
-    return {int(k): int(v) for k, v in kv[(kv[:, 0] != 0) | (kv[:, 1] != 0)]}
-
-
-def one_row(m, o, x, ys, vs):
-    both(m, o, SET, np.full(len(ys), x, np.uint32), np.asarray(ys, np.uint32), np.asarray(vs, np.uint32))
-
-
 # ---- case 1: the regimes -----------------------------------------------------------------------------------------------------
-# keys -> table: a table holds at most size / 2 keys, so these counts give 16, 512, 8192 (the wave path's last), 16384 and 32768
-# (one workgroup, one segment), 65536 and 131072 slots (2 and 4 segments: cut rows).  Values 1..5 (and 0 in row 11): ties everywhere.
-REGIMES = {10: (7, 16), 11: (200, 512), 12: (3000, 8192), 13: (6000, 16384), 14: (12000, 32768), 15: (20000, 65536), 16: (40000, 131072)}
+# the row shapes of tests/merge_helpers.REGIMES.  Values 1..5 (and 0 in row 11): ties everywhere.
 
 
 @pytest.fixture(scope="module")
@@ -94,6 +81,10 @@ def test_truncated_copy_of_every_regime(oracle_mod, regimes, m):
     assert dst.get(12, 0) == 1000 and dst.get(15, 0) == 3
     assert_export_equal(src.export("table"), table, "the source")
     dst.close(); o_dst.close()
+
+
+def test_rows_around_one_step_of_a_wave(oracle_mod):
+    check_rows_around_one_step(oracle_mod, merged_topk, column_totals=False)
 
 
 # ---- case 2: the digit passes ------------------------------------------------------------------------------------------------

@@ -13,12 +13,11 @@ import numpy as np
 import pytest
 
 from libsmatrix_amd import SparseMatrix
-from tests.merge_helpers import (DECR, GET, INCR, OPS, SET, assert_export_equal, both, check, device, ops_of, u32)  # noqa: F401
+from tests.merge_helpers import (DECR, GET, INCR, M_MAX, OPS, REGIMES, SET, assert_export_equal, both, check,  # noqa: F401
+                                 check_rows_around_one_step, device, one_row, ops_of, row_dict, u32)
 from tests.merge_topk_by_helpers import RANK_COSINE, RANK_VALUE, scores_of, topk_cosine
 
 pytestmark = pytest.mark.gpu
-
-M_MAX = 0xFFFFFFFF
 
 
 def merged_cos(dst, o_dst, src, cand, op, m, min_value, max_batch=0, tag=""):
@@ -31,15 +30,6 @@ def merged_cos(dst, o_dst, src, cand, op, m, min_value, max_batch=0, tag=""):
     assert (n, d) == (ops[0].size, dropped), (tag, (n, d), (ops[0].size, dropped))
     check(dst, o_dst, (before, cand), set(), tag)
     return ops, d
-
-
-def row_dict(m, x):
-    kv = m.row_slots(x)
-    return {int(k): int(v) for k, v in kv[(kv[:, 0] != 0) | (kv[:, 1] != 0)]}
-
-
-def one_row(m, o, x, ys, vs):
-    both(m, o, SET, np.full(len(ys), x, np.uint32), np.asarray(ys, np.uint32), np.asarray(vs, np.uint32))
 
 
 def set_totals(m, o, ids, totals):
@@ -67,11 +57,10 @@ def assert_model_scores_are_the_librarys(src, cand, tag=""):
 
 
 # ---- cases 1 and 2: the model's scores, the regimes ------------------------------------------------------------------------
-# The row shapes of tests/test_gpu_merge_topk.py: 16, 512 and 8192 slots (the wave path; 16: the keys held in registers), 16384 and
+# The row shapes of tests/merge_helpers.REGIMES: 16, 512 and 8192 slots (the wave path; 16: the keys held in registers), 16384 and
 # 32768 (one workgroup, one segment), 65536 and 131072 (cut rows of 2 and 4 segments).  The columns come from a pool of 42000 ids of
 # which 32000 have a row with a head total in 1..50 and 10000 have none (their total counts as 1); values 1..5, so a row of
 # thousands of pairs has 250 different scores at most: ties everywhere.  Rows 10 (short) and 14 (long) have no head pair.
-REGIMES = {10: (7, 16), 11: (200, 512), 12: (3000, 8192), 13: (6000, 16384), 14: (12000, 32768), 15: (20000, 65536), 16: (40000, 131072)}
 HEADS = {11: 400, 12: 1000, 13: 90, 15: 2500, 16: 37}
 POOL0, POOL, WITH_ROW = 100000, 42000, 32000
 
@@ -125,6 +114,10 @@ def test_truncated_copy_of_every_regime(oracle_mod, regimes, m):
         assert sorted(row_dict(dst, x)) == ys[:m].tolist()
     assert_export_equal(src.export("table"), table, "the source")
     dst.close(); o_dst.close()
+
+
+def test_rows_around_one_step_of_a_wave(oracle_mod):
+    check_rows_around_one_step(oracle_mod, merged_cos, column_totals=True)
 
 
 # ---- case 3: the digit passes ------------------------------------------------------------------------------------------------
