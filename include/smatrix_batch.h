@@ -156,6 +156,40 @@ int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const 
                                       const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids,
                                       double* d_scores, uint32_t* d_counts, void* hip_stream);
 
+/* Session recommendations by another similarity than the cosine, and with shrinkage: smatrix_cf_recommend_filtered with the
+ * score of a pair chosen by the caller.  What is not said here is smatrix_cf_recommend_filtered's contract, word for word:
+ * candidates, first positions, weights (w_a * score, the product rounded on its own), exclusion lists, the deny bitmap, counts,
+ * the result order (score descending, equal scores by ascending id), tiers, locks, streams, memory.
+ *   score      of the pair (b, cc) in the row of session item a, in place of cf_cosine(a, b).  ta = what smatrix_get(a, 0)
+ *              returns (0 without a row or a head pair), tb = smatrix_get(b, 0) with 0 counted as 1; A, B, c = ta, tb, cc as
+ *              doubles (exact).  Everything is IEEE double, sqrt * + - / correctly rounded:
+ *                  if (ta == 0) score = 0.0;                          every measure
+ *                  base = SMATRIX_SIM_COSINE   sqrt(A) * sqrt(B)
+ *                         SMATRIX_SIM_JACCARD  (A + B) - c            Jaccard / Tanimoto on co-occurrence counts
+ *                         SMATRIX_SIM_LIFT     A * B                  lift but for the constant factor: punishes popular b harder
+ *                  den   = base + shrink;                             base rounded to double ON ITS OWN, then one add: never a
+ *                                                                     fused multiply-add
+ *                  score = (den != 0.0 && !(c > den)) ? c / den : 0.0;
+ *              Scores lie in [0, 1] (a negative Jaccard denominator fails c > den and gives 0).  A session item with ta == 0 is
+ *              still an item: the keys of its row are candidates with a term of 0.0.
+ *   shrink     one finite double >= 0 for the call (-0.0 acts as 0.0), added to every denominator: a pair seen once between two
+ *              items seen once (cc = ta = tb = 1: cosine 1.0, the best possible score) no longer outranks a pair seen 200 times
+ *              between two common items.
+ * sim == SMATRIX_SIM_COSINE with shrink == 0 writes smatrix_cf_recommend_filtered's bytes (the same code path).
+ * Returns -1 for smatrix_cf_recommend_filtered's refusals, an unknown sim, and a shrink that is negative, NaN or infinite: shrink
+ * is a host scalar, so BOTH flavours refuse it before the device is touched and leave the outputs as they were.  0 otherwise.
+ * smatrix_cf_neighbors_batch and smatrix_cf_topk_batch stay cosine-only: an item's best neighbours by another measure are the
+ * result of this call for the session of that one item. */
+enum { SMATRIX_SIM_COSINE = 0, SMATRIX_SIM_JACCARD = 1, SMATRIX_SIM_LIFT = 2 };
+int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                             const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                             const uint32_t* deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* ids,
+                             double* scores, uint32_t* counts);
+int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                 const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                 const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k,
+                                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the
@@ -312,6 +346,21 @@ int smatrix_merge_topk(smatrix_t* dst, smatrix_t* src, int op, uint32_t m, uint3
 enum { SMATRIX_RANK_VALUE = 0, SMATRIX_RANK_COSINE = 1 };
 int smatrix_merge_topk_by(smatrix_t* dst, smatrix_t* src, int op, int rank, uint32_t m, uint32_t min_value,
                           uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped);
+
+/* smatrix_merge_topk_sim: smatrix_merge_topk_by(SMATRIX_RANK_COSINE) with the score of smatrix_cf_recommend_sim (above) in place of
+ *   the cosine, so that a serving copy is cut by the score it will be read by:
+ *   truncated by (sim, shrink), it answers smatrix_cf_recommend_sim(sim, shrink) for one-item sessions and k <= m as src does.
+ *   Everything not said here is smatrix_merge_topk_by's contract for the cosine rank, word for word: candidates, head pair,
+ *   eligibility, the rank key (bit pattern of the score, 0xFFFFFFFF - y: scores are >= 0, so the patterns order as the doubles
+ *   do; equal scores by ascending column), the op applied with the RAW v, the counts, the batch contract, locks, mirrors, files,
+ *   the one checkpoint, src untouched, and the 32 bytes of device memory per source ROW with nothing per pair.
+ *   The score of the pair (y, v) of row x is smatrix_cf_recommend_sim's with a = x, b = y, cc = v.  A row without a head pair
+ *   scores 0 everywhere and keeps its m LOWEST eligible columns; a dead cell scores 0, as does a pair with v > den.
+ * sim == SMATRIX_SIM_COSINE with shrink == 0 is smatrix_merge_topk_by(SMATRIX_RANK_COSINE) itself (the same code path).
+ * Returns 0; -1 and nothing changed (n_ops and n_dropped untouched) for an unknown sim, a shrink that is negative, NaN or
+ *   infinite, and for smatrix_merge_topk's refusals.  smatrix_merge_topk_by knows the two ranks above and no other. */
+int smatrix_merge_topk_sim(smatrix_t* dst, smatrix_t* src, int op, int sim, double shrink, uint32_t m, uint32_t min_value,
+                           uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped);
 int smatrix_import_csr(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* rows, const uint64_t* row_ptr,
                        const uint32_t* pairs, uint64_t max_batch, uint64_t* n_ops);
 int smatrix_import_csr_dev(smatrix_t* self, int op, uint64_t n_rows, const uint32_t* d_rows,

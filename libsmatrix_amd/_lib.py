@@ -76,6 +76,9 @@ def load():
         "smatrix_cf_recommend_filtered": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64,
                                                     C.c_uint32, u32p, C.POINTER(C.c_double), u32p]),
         "smatrix_cf_recommend_filtered_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, C.c_uint32, V, V, V, V]),
+        "smatrix_cf_recommend_sim": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64,
+                                               C.c_int, C.c_double, C.c_uint32, u32p, C.POINTER(C.c_double), u32p]),
+        "smatrix_cf_recommend_sim_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, C.c_int, C.c_double, C.c_uint32, V, V, V, V]),
         "smatrix_cf_import_sessions": (C.c_int, [H, C.c_size_t, u64p, u32p]),
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
         "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),
@@ -84,6 +87,7 @@ def load():
         "smatrix_merge_scaled": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
         "smatrix_merge_topk": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
         "smatrix_merge_topk_by": (C.c_int, [H, H, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
+        "smatrix_merge_topk_sim": (C.c_int, [H, H, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.c_uint64, u64p, u64p]),
         "smatrix_import_csr": (C.c_int, [H, C.c_int, C.c_uint64, u32p, u64p, u32p, C.c_uint64, u64p]),
         "smatrix_import_csr_dev": (C.c_int, [H, C.c_int, C.c_uint64, V, V, V, C.c_uint64, u64p, V]),
         "smatrix_stats": (None, [H, C.POINTER(Stats)]),

@@ -311,6 +311,8 @@ __global__ __launch_bounds__(1024) void k_mgx_count_big(const DirSlot* __restric
 // them; cnt[r] = the pairs the row keeps: min(m, eligible) + its head pair (y == 0) when v >= min_value.  What a key is, is a
 // policy (kernels/rank_key.hpp for the bits, below for what a key is made from):
 //   MgtValueKey    {v, ~y}.  Free to make: the counting pass ORs the keys as it goes.
+//   MgtSimKey      MgtCosineKey with the score of kernels/sim.hpp (smatrix_merge_topk_sim: Jaccard, lift, shrinkage); all that is
+//                  said of the cosine key below holds for it.
 //   MgtCosineKey   {the score's bits, ~y}.  The score of the pair (y, v) of row x is k_cf_neighbors' (kernels/rows.hpp), expression
 //                  for expression, in IEEE double:
 //                    tb = get(y, 0), 0 counted as 1;  den = sqrt(get(x, 0)) * sqrt(tb);  score = den != 0 && !(v > den) ? v / den : 0
@@ -450,6 +452,38 @@ struct MgtCosineKey : RkCosine {
   };
 };
 
+// smatrix_merge_topk_sim: MgtCosineKey's key with the score of kernels/sim.hpp -- the measure and its shrinkage travel with the
+// row's own double (sim_row: sqrt of the total for COSINE, the total otherwise)
+struct MgtSimKey : RkCosine {
+  static constexpr bool FREE = false, HOLD = true;
+  typedef MgtCosineKey::Thr Thr;
+  struct Row {
+    DirSlot* dir;
+    uint8_t* arena;
+    uint32_t dmask;
+    double ra;                                             // sim_row of the row's own total
+    SimArgs m;
+    __device__ __forceinline__ Key key(uint32_t y, uint32_t v) const {
+      bool dummy = false;
+      const double cb = sim_col(m.sim, apply_one<OP_GET>(dir, dmask, arena, y, 0u, 0u, &dummy));
+      return make(y, (uint64_t)__double_as_longlong(sim_score(m, v, ra, cb)));
+    }
+  };
+  struct Src {
+    DirSlot* dir;
+    uint8_t* arena;
+    const uint64_t* items;
+    uint32_t dmask;
+    SimArgs m;
+    __device__ __forceinline__ Row blank() const { return Row{dir, arena, dmask, 0.0, m}; }
+    __device__ __forceinline__ Row row(uint32_t x) const {
+      bool dummy = false;
+      return Row{dir, arena, dmask, sim_row(m.sim, apply_one<OP_GET>(dir, dmask, arena, x, 0u, 0u, &dummy)), m};
+    }
+    __device__ __forceinline__ Row at(uint32_t r) const { return row(dir[(uint32_t)(items[r] >> 32)].x); }
+  };
+};
+
 // the emission's filter: the pairs of row r whose rank key is at least the row's threshold, and the head pair
 template <typename P>
 struct MgRankRow {
@@ -476,6 +510,7 @@ struct MgRank {
 };
 using MgTopk = MgRank<MgtValueKey>;
 using MgCos = MgRank<MgtCosineKey>;
+using MgSim = MgRank<MgtSimKey>;
 
 __device__ __forceinline__ bool mgt_eligible(uint32_t key, uint32_t val, uint32_t min_value) { return key != 0 && val >= min_value; }
 
@@ -890,6 +925,156 @@ __global__ __launch_bounds__(1024) void k_mgc_emit_big(const DirSlot* __restrict
                                                        const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
                                                        const uint32_t* big, uint32_t* seg_cnt, const MgCos f) {
   mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f);
+}
+
+// ---- smatrix_merge_topk_sim: the four kernels over MgtSimKey ------------------------------------------------------------------
+// The workgroup-per-row selection, written ONCE over a key policy of RkCosine's shape (a 96-bit key that costs a gather: no key
+// in the counting pass, the start from the OR and the AND of the keys): k_mgc_select_big's steps, with the key arithmetic taken
+// from the policy.  k_mgc_select_big itself stays written out (see above: the fold measured slower for the value key, and the
+// cosine kernel's registers are pinned by the build it was written with); a third written-out copy would add nothing.
+template <typename P>
+__device__ __forceinline__ void mgr_select_big_rows(const DirSlot* dir, uint8_t* arena, const uint64_t* __restrict__ items, uint32_t m,
+                                                    uint32_t min_value, const typename P::Src src, const typename P::Thr thr,
+                                                    uint32_t* __restrict__ cnt, const uint32_t* big, unsigned long long* tot) {
+  typedef typename P::Key Key;
+  static_assert(P::W == 3 && !P::FREE, "a 96-bit key made by a gather");
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256];
+  __shared__ uint32_t wacc[6][16];                         // per wave: eligible, seen, head; then the six words of P::Acc
+  __shared__ uint32_t acc[8];                              // 2 .. 4: the key found; 5 .. 7: d, above, bucket
+  auto uni = [&](uint32_t i) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)acc[i]); };   // (scalar control flow)
+  const uint32_t nent = big[0];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (uint32_t e = blockIdx.x; e < nent; e += gridDim.x) {
+    const uint32_t r = big[1 + e];
+    const uint4 s = *reinterpret_cast<const uint4*>(&dir[(uint32_t)(items[r] >> 32)]);
+    const uint32_t size = 1u << meta_lg(s.x);                          // > GETROW_WAVE_MAX: a multiple of 2048
+    const uint4* cells = reinterpret_cast<const uint4*>(row_cells(arena, s.z));
+    {
+      uint32_t elig = 0, seen = 0, head = 0;
+      for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+        const uint4 q = cells[(p0 >> 1) + threadIdx.x];
+        seen += ((q.x | q.y) != 0) + ((q.z | q.w) != 0);
+        head |= (q.x == 0 && q.y != 0 && q.y >= min_value) | (q.z == 0 && q.w != 0 && q.w >= min_value);
+        elig += mgt_eligible(q.x, q.y, min_value) + mgt_eligible(q.z, q.w, min_value);
+      }
+      elig = mg_wave_sum(elig); seen = mg_wave_sum(seen); head = mg_wave_or(head);
+      if (lane == 0) { wacc[0][w] = elig; wacc[1][w] = seen; wacc[2][w] = head; }
+    }
+    __syncthreads();
+    uint32_t elig = 0, seen = 0, head = 0;
+    for (uint32_t i = 0; i < 16; i++) { elig += wacc[0][i]; seen += wacc[1][i]; head |= wacc[2][i]; }
+    elig = (uint32_t)__builtin_amdgcn_readfirstlane((int)elig);
+    if (threadIdx.x == 0 && seen) atomicAdd(tot, (unsigned long long)seen);
+    Key t = P::zero();
+    if (elig > m) {                                                    // (from LDS: the same on every lane)
+      const typename P::Row row = src.row(s.y);
+      __syncthreads();                                                 // (wacc was read by every lane)
+      {
+        typename P::Acc a = P::acc0();
+        for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+          const MgtPair<Key> k = mgt_keys<P>(row, min_value, cells[(p0 >> 1) + threadIdx.x]);
+          if (k.e0) P::acc_add(a, k.k0);
+          if (k.e1) P::acc_add(a, k.k1);
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 6; i++) { const uint32_t v = mg_wave_or(a.w[i]); if (lane == 0) wacc[i][w] = v; }
+      }
+      __syncthreads();
+      uint32_t need = m;
+      typename P::Acc a = P::acc0();
+#pragma unroll
+      for (uint32_t i = 0; i < 6; i++) {
+        uint32_t v = 0;
+        for (uint32_t j = 0; j < 16; j++) v |= wacc[i][j];
+        a.w[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+      }
+      Key prefix;
+      uint32_t dg = P::start(a, prefix);
+      for (;;) {
+        __syncthreads();                                               // (acc and hist were read by every lane)
+        if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (uint32_t p0 = 0; p0 < size; p0 += 2048) {
+          const MgtPair<Key> k = mgt_keys<P>(row, min_value, cells[(p0 >> 1) + threadIdx.x]);
+          mgt_hist_add(hist, k.e0 && P::agrees_above(k.k0, prefix, dg), P::digit(k.k0, dg), lane);
+          mgt_hist_add(hist, k.e1 && P::agrees_above(k.k1, prefix, dg), P::digit(k.k1, dg), lane);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+          uint32_t d, above, bucket;
+          mgt_pick<true>(hist, need, lane, d, above, bucket);
+          if (lane == 0) { acc[5] = d; acc[6] = above; acc[7] = bucket; }
+        }
+        __syncthreads();
+        need -= uni(6);
+        P::take_digit(prefix, dg, uni(5));
+        if (dg == 0) break;
+        if (uni(7) == 1) {
+          if (threadIdx.x < 3) acc[2 + threadIdx.x] = 0;
+          __syncthreads();
+          for (uint32_t p0 = 0; p0 < size; p0 += 2048) {               // (one lane of the workgroup: keys are unique)
+            const MgtPair<Key> k = mgt_keys<P>(row, min_value, cells[(p0 >> 1) + threadIdx.x]);
+            const bool h0 = k.e0 && P::agrees_down(k.k0, prefix, dg), h1 = k.e1 && P::agrees_down(k.k1, prefix, dg);
+            if (h0 || h1) {
+              uint32_t kw[3] = {0, 0, 0};
+              P::or_words(kw, h0 ? k.k0 : k.k1);
+              acc[2] = kw[0]; acc[3] = kw[1]; acc[4] = kw[2];
+            }
+          }
+          __syncthreads();
+          const uint32_t kw[3] = {uni(2), uni(3), uni(4)};
+          prefix = P::from_words(kw);
+          break;
+        }
+        dg--;
+      }
+      t = prefix;
+    }
+    if (threadIdx.x == 0) { thr.store(r, t); cnt[r] = (elig < m ? elig : m) + head; }
+    __syncthreads();                                                   // (wacc and acc are the next row's)
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mgs_select(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t n,
+                                                    const uint64_t* __restrict__ items, uint32_t m, uint32_t min_value, const SimArgs sim,
+                                                    uint64_t* __restrict__ thr, uint32_t* __restrict__ thr_col,
+                                                    uint32_t* __restrict__ cnt, uint32_t* big, unsigned long long* tot) {
+  mgt_select_rows<MgtSimKey>(dir, arena, n, items, m, min_value, {dir, arena, items, dmask, sim}, {thr, thr_col}, cnt, big, tot,
+                             (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
+}
+
+__global__ __launch_bounds__(1024) void k_mgs_select_big(DirSlot* dir, uint32_t dmask, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                         uint32_t m, uint32_t min_value, const SimArgs sim, uint64_t* __restrict__ thr,
+                                                         uint32_t* __restrict__ thr_col, uint32_t* __restrict__ cnt, const uint32_t* big,
+                                                         unsigned long long* tot) {
+  mgr_select_big_rows<MgtSimKey>(dir, arena, items, m, min_value, {dir, arena, items, dmask, sim}, {thr, thr_col}, cnt, big, tot);
+}
+
+// The emission's filter as the kernels take it: MgSim without the directory, the arena and the row list, which every emission
+// kernel is handed anyway -- as a second copy in the argument they are six scalar registers the compiler cannot tell from the
+// first, and k_mgs_emit_big<false> has none to spare.
+struct MgSimArgs {
+  uint64_t* thr;
+  uint32_t* thr_col;
+  uint32_t dmask, min_value;
+  SimArgs sim;
+  __device__ __forceinline__ MgSim over(const DirSlot* dir, uint8_t* arena, const uint64_t* items) const {
+    return MgSim{{thr, thr_col}, {const_cast<DirSlot*>(dir), arena, items, dmask, sim}, min_value};
+  }
+};
+
+__global__ __launch_bounds__(256) void k_mgs_emit(const DirSlot* dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                  const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t r1,
+                                                  uint32_t* __restrict__ rec, uint32_t* big, const MgSimArgs f) {
+  mg_emit_rows(dir, arena, items, ptr, r0, r1, rec, big, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6,
+               f.over(dir, arena, items));
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(1024) void k_mgs_emit_big(const DirSlot* dir, uint8_t* arena, const uint64_t* __restrict__ items,
+                                                       const uint64_t* __restrict__ ptr, uint32_t r0, uint32_t* __restrict__ rec,
+                                                       const uint32_t* big, uint32_t* seg_cnt, const MgSimArgs f) {
+  mg_emit_segs<COUNT>(dir, arena, items, ptr, r0, rec, big, seg_cnt, f.over(dir, arena, items));
 }
 
 // ---- from a CSR in smatrix_export's layout ------------------------------------------------------------------------------------

@@ -18,6 +18,9 @@
 //                   an ITEM's first position, and an id may be both); the table has room for them (k_rec_bound)
 //   deny bitmap     tested where a key is claimed: a denied key gets sqrt = -1 like an item
 //   weights         the term of the item at position i is multiplied by w[i] (__dmul_rn: rounded on its own) before it is added
+// smatrix_cf_recommend_sim (RecFilt::m; k_rec_lds_sim<F>, k_rec_gl_scan_sim<F>: the two kernels that make a score, over the same
+// bodies): the term is kernels/sim.hpp's, the per-row double sqrt(A) or A, the slot's double sqrt(B) or B.  The tiers, the
+// tables and the top-k know nothing of the measure: k_rec_bound, k_rec_gl_init and the rest are the filtered call's.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -38,6 +41,7 @@ struct RecFilt {
   const uint32_t* ex;
   const uint32_t* deny;                       // bit b & 31 of word b >> 5: id b < deny_n is never given
   uint64_t deny_n;
+  SimArgs m;                                  // smatrix_cf_recommend_sim: the measure and its shrinkage (read by the <.., true> bodies alone)
 };
 __device__ __forceinline__ bool rec_denied(const RecFilt& f, uint32_t b) {
   return b < f.deny_n && ((f.deny[b >> 5] >> (b & 31)) & 1u) != 0;
@@ -51,15 +55,28 @@ struct CfById {
   }
 };
 
-// one term, exactly as k_cf_neighbors computes it (sqb = sqrt of get(b,0), 0 counted as 1)
-__device__ __forceinline__ double rec_term(uint32_t cc, double sa, double sqb) {
+// one term.  <false>: exactly as k_cf_neighbors computes it (sa = sqrt of get(a,0); sqb = sqrt of get(b,0), 0 counted as 1).
+// <true>: the measure m (kernels/sim.hpp) over the same two cached doubles, sa = sim_row of get(a,0), sqb = sim_col of get(b,0)
+template <bool S>
+__device__ __forceinline__ double rec_term(uint32_t cc, double sa, double sqb, const SimArgs& m) {
+  if (S) return sim_score(m, cc, sa, sqb);
   const double num = (double)cc;
   const double den = sa * sqb;
   return (den != 0.0 && !(num > den)) ? num / den : 0.0;
 }
-__device__ __forceinline__ double rec_sqrt_total(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t b) {
+// the row's double of item a, and the candidate's of key b: what a slot caches (always >= 1, so 0.0 = not yet filled and
+// -1 = an excluded key keep their meaning under every measure)
+template <bool S>
+__device__ __forceinline__ double rec_row_total(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t a, const SimArgs& m) {
+  bool dummy = false;
+  const uint32_t t = apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy);
+  return S ? sim_row(m.sim, t) : sqrt((double)t);
+}
+template <bool S>
+__device__ __forceinline__ double rec_col_total(DirSlot* dir, uint32_t dmask, uint8_t* arena, uint32_t b, const SimArgs& m) {
   bool dummy = false;
   uint32_t t = apply_one<OP_GET>(dir, dmask, arena, b, 0u, 0u, &dummy);
+  if (S) return sim_col(m.sim, t);
   if (t == 0) t = 1;
   return sqrt((double)t);
 }
@@ -161,12 +178,13 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 }
 
 // ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
-template <bool F>
-__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
-                                                             const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
-                                                             const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
-                                                             uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
-                                                             uint32_t* __restrict__ counts, RecFilt f) {
+// (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's)
+template <bool F, bool S>
+__device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                        const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                        const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
+                                        uint32_t* __restrict__ ids, double* __restrict__ scores, uint32_t* __restrict__ counts,
+                                        const RecFilt& f) {
   __shared__ uint32_t s_key[REC_LDS_SLOTS];
   __shared__ double s_sq[REC_LDS_SLOTS];
   __shared__ double s_sum[REC_LDS_SLOTS];
@@ -210,8 +228,7 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
       }
       uint4 sn;
       if (!dir_find(dir, dmask, a, &sn) || sn.z == 0) continue;
-      bool dummy = false;
-      const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+      const double sa = rec_row_total<S>(dir, dmask, arena, a, f.m);
       const double wa = F && f.w ? f.w[b0 + i] : 1.0;
       const uint32_t size = 1u << meta_lg(sn.x);
       const uint64_t* cells = row_cells(arena, sn.z);
@@ -224,16 +241,16 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
         double sqb;
         if (claimed) {
           if (F && rec_denied(f, b)) { s_sq[h] = -1.0; continue; }  // a denied key: excluded from here on
-          sqb = rec_sqrt_total(dir, dmask, arena, b);
+          sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
           s_sq[h] = sqb;
         } else {
           sqb = s_sq[h];
           if (sqb < 0.0) continue;                                  // an item of the session, an excluded or a denied key
           // claimed by another lane of this row (a twice-held key).  If that lane is about to deny the key, this term is added
           // to a sum nobody reads: the selection below takes s_sq > 0 after the barrier
-          if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);
+          if (sqb == 0.0) sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
         }
-        double term = rec_term(cell_val(c), sa, sqb);
+        double term = rec_term<S>(cell_val(c), sa, sqb, f.m);
         if (F) term = __dmul_rn(wa, term);                          // (rounded before the add; wa == 1.0 changes no bit)
         __hip_atomic_fetch_add(&s_sum[h], term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
@@ -275,6 +292,23 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
     }
     __syncthreads();                                                // before the next session clears the table
   }
+}
+
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                             const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                             const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                             uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                             uint32_t* __restrict__ counts, RecFilt f) {
+  rec_lds<F, false>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f);
+}
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_sim(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                 const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                 const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                 uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                 uint32_t* __restrict__ counts, RecFilt f) {
+  rec_lds<F, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f);
 }
 
 // ---- global tier -----------------------------------------------------------------------------------------------------------
@@ -359,10 +393,11 @@ __global__ __launch_bounds__(256) void k_rec_gl_plan(RecGl R, DirSlot* dir, uint
 }
 
 // position p = p0 + j: a wave per chunk task; scan[j * n_big + idx] = the first task of session idx (scan of k_rec_gl_plan's counts)
-template <bool F>
-__global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
-                                                     const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
-                                                     uint32_t j, const uint64_t* __restrict__ scan, RecFilt f) {
+// (the body of k_rec_gl_scan<F> and of k_rec_gl_scan_sim<F>, as rec_lds)
+template <bool F, bool S>
+__device__ __forceinline__ void rec_gl_scan(const RecGl& R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
+                                            const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
+                                            uint32_t j, const uint64_t* __restrict__ scan, const RecFilt& f) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
   const uint64_t* sc = scan + (uint64_t)j * R.n_big;
@@ -378,8 +413,7 @@ __global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint
     const uint32_t a = items[off[s] + p0 + j];
     uint4 sn;
     dir_find(dir, dmask, a, &sn);                                   // (there: the plan gave it chunks)
-    bool dummy = false;
-    const double sa = sqrt((double)apply_one<OP_GET>(dir, dmask, arena, a, 0u, 0u, &dummy));
+    const double sa = rec_row_total<S>(dir, dmask, arena, a, f.m);
     const double wa = F && f.w ? f.w[off[s] + p0 + j] : 1.0;
     const uint32_t size = 1u << meta_lg(sn.x);
     const uint64_t* cells = row_cells(arena, sn.z);
@@ -401,18 +435,31 @@ __global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint
       double sqb;
       if (claimed) {
         if (F && rec_denied(f, b)) { sq[h] = -1.0; continue; }
-        sqb = rec_sqrt_total(dir, dmask, arena, b);
+        sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
         sq[h] = sqb;
       } else {
         sqb = __hip_atomic_load(&sq[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (sqb < 0.0) continue;
-        if (sqb == 0.0) sqb = rec_sqrt_total(dir, dmask, arena, b);   // (a denied key's claimer may be between its claim and its
+        if (sqb == 0.0) sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);   // (a denied key's claimer may be between its claim and its
       }                                                               // store: as in k_rec_lds, k_rec_gl_topk reads gq > 0 later)
-      double term = rec_term(cell_val(cv[u]), sa, sqb);
+      double term = rec_term<S>(cell_val(cv[u]), sa, sqb, f.m);
       if (F) term = __dmul_rn(wa, term);
       unsafeAtomicAdd(&sum[h], term);
     }
   }
+}
+
+template <bool F>
+__global__ __launch_bounds__(256) void k_rec_gl_scan(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
+                                                     const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
+                                                     uint32_t j, const uint64_t* __restrict__ scan, RecFilt f) {
+  rec_gl_scan<F, false>(R, dir, dmask, arena, off, items, p0, j, scan, f);
+}
+template <bool F>
+__global__ __launch_bounds__(256) void k_rec_gl_scan_sim(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
+                                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
+                                                         uint32_t j, const uint64_t* __restrict__ scan, RecFilt f) {
+  rec_gl_scan<F, true>(R, dir, dmask, arena, off, items, p0, j, scan, f);
 }
 
 // a wave per REC_SEG-slot segment of the group's tables: its 64 best -> lk / li (64 entries per segment, best first)

@@ -33,6 +33,7 @@ namespace smx {
 #include "kernels/rows.hpp"
 #include "kernels/export.hpp"
 #include "kernels/rank_key.hpp"
+#include "kernels/sim.hpp"
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
 #include "kernels/io_router.hpp"

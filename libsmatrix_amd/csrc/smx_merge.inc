@@ -1,4 +1,4 @@
-// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_merge_topk_by / smatrix_import_csr /
+// smx_merge.inc -- smatrix_merge / smatrix_merge_scaled / smatrix_merge_topk / smatrix_merge_topk_by / _sim / smatrix_import_csr /
 // smatrix_import_csr_dev (include/smatrix_batch.h), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses its ExportScratch, ex_row_list, ex_measure
 // and scan); the device code is kernels/merge.hpp.
@@ -22,7 +22,8 @@
 // merge_topk, merge_topk_by: the same with the counts and a threshold per row from the selection (mg_count_selected); the emission
 //        filters by that threshold and counts a cut row's segments batch by batch, as merge does.  By value (k_mgt_*) the threshold
 //        is 8 bytes, 28 bytes per row; by cosine (k_mgc_*) 12, its score half in thr and its column half in thr_col, 32 bytes per
-//        row and no score per pair.
+//        row and no score per pair.  merge_topk_sim (k_mgs_*) is the cosine flavour with the measure and its shrinkage as two
+//        more kernel arguments: the same 32 bytes per row.
 
 namespace {
 
@@ -67,6 +68,14 @@ void merge_release(Matrix* m) {
   delete g;
   m->mg = nullptr;
 }
+
+// the measure and the shrinkage of smatrix_merge_topk_sim and smatrix_cf_recommend_sim (smx_recommend.inc): a known measure, a
+// finite shrink >= 0 (-0.0 passes, NaN fails); the plain cosine is the existing code path of both
+static_assert(SIM_COSINE == SMATRIX_SIM_COSINE && SIM_JACCARD == SMATRIX_SIM_JACCARD && SIM_LIFT == SMATRIX_SIM_LIFT, "kernels/sim.hpp");
+bool sim_args_ok(int sim, double shrink) {
+  return (sim == SMATRIX_SIM_COSINE || sim == SMATRIX_SIM_JACCARD || sim == SMATRIX_SIM_LIFT) && shrink >= 0.0 && std::isfinite(shrink);
+}
+bool sim_is_plain_cosine(int sim, double shrink) { return sim == SMATRIX_SIM_COSINE && shrink == 0.0; }
 
 bool mg_op_ok(int op) { return op == OP_SET || op == OP_INCR || op == OP_DECR; }
 uint64_t mg_batch(uint64_t max_batch) { return max_batch == 0 ? MG_DEFAULT_BATCH : std::min(max_batch, MG_MAX_BATCH); }
@@ -378,6 +387,24 @@ int smatrix_merge_topk_by(smatrix_t* dst, smatrix_t* src, int op, int rank, uint
     [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
       mg_emit_topk(c, k_mgc_emit, k_mgc_emit_big<true>, k_mgc_emit_big<false>, r0, r1, rec, e,
                    MgCos{{c.g.thr.p, c.g.thr_col.p}, {c.sm->d_dir, c.sm->arena.base, c.x.items.p, c.sm->dir_size - 1}, min_value});
+    });
+}
+
+int smatrix_merge_topk_sim(smatrix_t* dst, smatrix_t* src, int op, int sim, double shrink, uint32_t m, uint32_t min_value,
+                           uint64_t max_batch, uint64_t* n_ops, uint64_t* n_dropped) {
+  if (!sim_args_ok(sim, shrink)) return -1;
+  if (sim_is_plain_cosine(sim, shrink))
+    return smatrix_merge_topk_by(dst, src, op, SMATRIX_RANK_COSINE, m, min_value, max_batch, n_ops, n_dropped);
+  if (m == 0) return -1;
+  const SimArgs f{sim, shrink};
+  return mg_merge(dst, src, op, max_batch, n_ops, n_dropped,
+    mg_count_selected("merge_topk_sim", true, k_mgs_select, k_mgs_select_big, [=](MergeCall& c, auto kernel, dim3 grid, dim3 lanes, auto... n) {
+      hipLaunchKernelGGL(kernel, grid, lanes, 0, c.s, c.sm->d_dir, c.sm->dir_size - 1, c.sm->arena.base, n..., c.x.items.p, m, min_value, f,
+                         c.g.thr.p, c.g.thr_col.p, c.x.cnt.p, c.g.big.p, c.g.tot.p);
+    }),
+    [&](const MergeCall& c, uint32_t r0, uint32_t r1, uint32_t* rec, hipStream_t e) {
+      mg_emit_topk(c, k_mgs_emit, k_mgs_emit_big<true>, k_mgs_emit_big<false>, r0, r1, rec, e,
+                   MgSimArgs{c.g.thr.p, c.g.thr_col.p, c.sm->dir_size - 1, min_value, f});
     });
 }
 

@@ -1,5 +1,5 @@
-// smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev and
-// smatrix_cf_recommend_filtered / _dev), host side.
+// smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
+// smatrix_cf_recommend_filtered / _dev and smatrix_cf_recommend_sim / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -11,6 +11,8 @@
 //      kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
 // The filtered call is the same driver with a RecFilt (weights, exclusion lists, deny bitmap) and the kernels' <true> instances;
 // with nothing given it runs the <false> ones, the code of smatrix_cf_recommend_batch.
+// The sim call is the filtered call with a measure and a shrinkage in the RecFilt and, for the two kernels that make a score,
+// their _sim instances; with SMATRIX_SIM_COSINE and shrink 0 it IS the filtered call.
 
 namespace {
 
@@ -79,8 +81,9 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
 }
 
 // the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back).
-// F: the filtered call with something given in f.  -1 (nothing but k_rec_bound has run) for a bad weight, 0 otherwise
-template <bool F>
+// F: the filtered call with something given in f; S: the sim call, the score is f.m's.  -1 (nothing but k_rec_bound has run) for
+// a bad weight, 0 otherwise
+template <bool F, bool S>
 int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
             uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f) {
   DirSlot* dir = m->d_dir;
@@ -95,7 +98,7 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   HIP_OK(hipStreamSynchronize(s));
   if (F && c.bad) return -1;
   if (c.n_lds)
-    hipLaunchKernelGGL(k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
+    hipLaunchKernelGGL(S ? k_rec_lds_sim<F> : k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
                        x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
   HIP_OK(hipGetLastError());
   if (!c.n_big) return 0;
@@ -123,8 +126,8 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
       HIP_OK(hipGetLastError());
       rec_scan(x, s, x.cnt.p, nt, x.scan.p);
       for (uint32_t j = 0; j < nj; j++)
-        hipLaunchKernelGGL(k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off, d_items, p0, j, x.scan.p,
-                           f);
+        hipLaunchKernelGGL(S ? k_rec_gl_scan_sim<F> : k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off,
+                           d_items, p0, j, x.scan.p, f);
       HIP_OK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, R, nseg, k, x.lk.p,
@@ -144,6 +147,89 @@ bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_
   return (ex_offsets == nullptr) == (ex_items == nullptr);
 }
 bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
+// (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
+
+// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure
+int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
+                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim) {
+  if (sim) return rec_filt_any(f) ? rec_run<true, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f)
+                                  : rec_run<false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f);
+  return rec_filt_any(f) ? rec_run<true, false>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f)
+                         : rec_run<false, false>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f);
+}
+
+// smatrix_cf_recommend_filtered_dev and smatrix_cf_recommend_sim_dev behind their refusals; sim: score by f_m, not by the cosine
+int rec_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
+                     const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k,
+                     uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream, bool sim, SimArgs f_m) {
+  if (n_sessions == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, f_m};
+  const int rc = rec_dispatch(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim);
+  rec_end(x, s);
+  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
+  rec_trim_all(x, false);
+  return rc;
+}
+
+// the host flavours of the same two
+int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                      const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
+                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m) {
+  if (n_sessions == 0) return 0;
+  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
+  if (weights)
+    for (uint64_t i = 0; i < n_items; i++)
+      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = m->stream;
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
+  std::vector<uint64_t> rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
+  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
+  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
+  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
+  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
+  RecFilt f{};
+  f.m = f_m;
+  if (weights) {
+    x.h_w.need(std::max<uint64_t>(n_items, 1));
+    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
+    f.w = x.h_w.p;
+  }
+  if (ex_offsets) {
+    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
+    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
+    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
+  }
+  if (deny_n) {
+    x.h_deny.need(n_deny);
+    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
+    f.deny = x.h_deny.p; f.deny_n = deny_n;
+  }
+  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as smatrix_cf_recommend_batch's
+  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
+  rec_dispatch(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim);
+  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
+  rec_end(x, s);
+  HIP_OK(hipStreamSynchronize(s));
+  rec_trim_all(x, false);
+  return 0;
+}
 
 void recommend_release(Matrix* m) {
   if (!m->rec) return;
@@ -169,7 +255,7 @@ int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uin
   hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
   RecScratch& x = rec_of(m);
   rec_begin(x, s);
-  rec_run<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{});
+  rec_run<false, false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{});
   rec_end(x, s);
   if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
   rec_trim_all(x, false);
@@ -195,7 +281,7 @@ int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_
   if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as cf_topk_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_run<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{});
+  rec_run<false, false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{});
   HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
@@ -210,21 +296,8 @@ int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const 
                                       const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids, double* d_scores,
                                       uint32_t* d_counts, void* hip_stream) {
   if (!rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n};
-  const int rc = rec_filt_any(f) ? rec_run<true>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f)
-                                 : rec_run<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f);
-  rec_end(x, s);
-  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
-  rec_trim_all(x, false);
-  return rc;
+  return rec_filtered_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k, d_ids,
+                          d_scores, d_counts, hip_stream, false, SimArgs{});
 }
 
 int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
@@ -232,53 +305,25 @@ int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint
                                   const uint32_t* deny_bits, uint64_t deny_n, uint32_t k, uint32_t* ids, double* scores,
                                   uint32_t* counts) {
   if (!rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
-  if (n_sessions == 0) return 0;
-  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
-  if (weights)
-    for (uint64_t i = 0; i < n_items; i++)
-      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = m->stream;
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
-  std::vector<uint64_t> rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
-  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
-  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
-  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
-  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
-  RecFilt f{};
-  if (weights) {
-    x.h_w.need(std::max<uint64_t>(n_items, 1));
-    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
-    f.w = x.h_w.p;
-  }
-  if (ex_offsets) {
-    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
-    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
-    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
-  }
-  if (deny_n) {
-    x.h_deny.need(n_deny);
-    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
-    f.deny = x.h_deny.p; f.deny_n = deny_n;
-  }
-  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as smatrix_cf_recommend_batch's
-  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  if (rec_filt_any(f)) rec_run<true>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
-  else rec_run<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
-  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
-  rec_end(x, s);
-  HIP_OK(hipStreamSynchronize(s));
-  rec_trim_all(x, false);
-  return 0;
+  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
+                           false, SimArgs{});
+}
+
+int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                 const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                 const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* d_ids,
+                                 double* d_scores, uint32_t* d_counts, void* hip_stream) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
+  return rec_filtered_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k, d_ids,
+                          d_scores, d_counts, hip_stream, !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
+}
+
+int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                             const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
+                             double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
+  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
+                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
 }
 
 }  // extern "C"

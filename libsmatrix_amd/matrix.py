@@ -57,16 +57,46 @@ def _topk_args(m, min_value):
 
 
 _RANKS = {"value": 0, "cosine": 1}                      # SMATRIX_RANK_VALUE, SMATRIX_RANK_COSINE
+_SIMS = {"cosine": 0, "jaccard": 1, "lift": 2}          # SMATRIX_SIM_COSINE, SMATRIX_SIM_JACCARD, SMATRIX_SIM_LIFT
 
 
 def _rank(rank):
-    """"value" / "cosine" -> the rank code; anything else is a ValueError"""
-    if isinstance(rank, str) and rank in _RANKS:
-        return _RANKS[rank]
-    raise ValueError("rank must be 'value' or 'cosine', not %r" % (rank,))
+    """"value" / "cosine" / "jaccard" / "lift" -> the name; anything else is a ValueError"""
+    if isinstance(rank, str) and (rank in _RANKS or rank in _SIMS):
+        return rank
+    raise ValueError("rank must be 'value', 'cosine', 'jaccard' or 'lift', not %r" % (rank,))
+
+
+def _sim(sim):
+    """"cosine" / "jaccard" / "lift" -> the measure's code; anything else is a ValueError"""
+    if isinstance(sim, str) and sim in _SIMS:
+        return _SIMS[sim]
+    raise ValueError("sim must be 'cosine', 'jaccard' or 'lift', not %r" % (sim,))
+
+
+def _shrink(shrink):
+    """the shrinkage added to a score's denominator: a finite real number >= 0 -> float; anything else is a ValueError"""
+    if isinstance(shrink, (bool, str)) or not isinstance(shrink, (int, float, np.integer, np.floating)):
+        raise ValueError("shrink must be a finite number >= 0, not %r" % (shrink,))
+    h = float(shrink)
+    if not (h >= 0.0 and h != float("inf")):
+        raise ValueError("shrink must be a finite number >= 0, not %r" % (shrink,))
+    return h
+
+
+def _rank_args(rank, shrink):
+    """merge_topk's rank / shrink -> (rank name, shrink as float); shrink != 0 needs a rank that scores"""
+    rank, h = _rank(rank), _shrink(shrink)
+    if rank == "value" and h != 0.0:
+        raise ValueError("shrink belongs to a score: rank='value' takes none")
+    return rank, h
 
 
 def _topk_by_args(rank, m, min_value):
+    _topk_args(m, min_value)
+
+
+def _topk_sim_args(sim, shrink, m, min_value):
     _topk_args(m, min_value)
 
 
@@ -283,12 +313,16 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
 
-    def cf_recommend_filtered(self, sessions, k, weights=None, exclude=None, deny=None):
+    def cf_recommend_filtered(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_batch with "not these" and recency (include/smatrix_batch.h smatrix_cf_recommend_filtered), applied on
         the GPU before the k best are taken.  weights: per-session sequences shaped like sessions, finite and >= 0 (the term of
         an item is multiplied by the weight at its first position); exclude: one id sequence per session, never given to it;
-        deny: ids given to no session.  -> (ids[n,k], scores[n,k] float64, counts[n]) as cf_recommend_batch"""
+        deny: ids given to no session.  -> (ids[n,k], scores[n,k] float64, counts[n]) as cf_recommend_batch.
+        sim, shrink (smatrix_cf_recommend_sim): the score of a pair (b, cc) of item a is cc / (base + shrink) with base =
+        sqrt(A) * sqrt(B) ("cosine"), A + B - cc ("jaccard") or A * B ("lift") over the totals A = self[a, 0], B = self[b, 0];
+        shrink is a finite number >= 0.  The defaults make the call above"""
         _check_k(k)
+        code, h = _sim(sim), _shrink(shrink)
         n = len(sessions)
         w = None if weights is None else _weights(weights, sessions)
         if exclude is not None and len(exclude) != n:
@@ -300,12 +334,15 @@ class SparseMatrix:
         scores = np.zeros((n, k), dtype=np.float64)
         counts = np.zeros(n, dtype=np.uint32)
         dp = C.POINTER(C.c_double)
-        if n and self._lib.smatrix_cf_recommend_filtered(
-                self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
-                None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
-                None if bits is None else _p(bits), deny_n, k, ids.ctypes.data_as(_lib.u32p), scores.ctypes.data_as(dp),
-                _p(counts)) != 0:
-            raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
+        front = (self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
+                 None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
+                 None if bits is None else _p(bits), deny_n)
+        back = (k, ids.ctypes.data_as(_lib.u32p), scores.ctypes.data_as(dp), _p(counts))
+        if code == 0 and h == 0.0:
+            if n and self._lib.smatrix_cf_recommend_filtered(*front, *back) != 0:
+                raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
+        elif n and self._lib.smatrix_cf_recommend_sim(*front, code, h, *back) != 0:
+            raise ValueError("smatrix_cf_recommend_sim: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
         return ids, scores, counts
 
     def cf_recommend_filtered_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, k, ids_ptr,
@@ -318,6 +355,16 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_filtered_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
                                                        deny_n, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_filtered_dev: bad k, n, weights, exclusion lists or deny bitmap")
+
+    def cf_recommend_sim_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, k,
+                             ids_ptr, scores_ptr, cnt_ptr, stream=None):
+        """cf_recommend_filtered_dev with cf_recommend_filtered's sim and shrink (smatrix_cf_recommend_sim_dev)"""
+        _check_k(k)
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_sim_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
+                                                  deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_sim_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
 
     def cf_import_sessions(self, sessions):
         """CF-recommender write path (examples/cf_recommender.c:36-47): every session is a sequence of item ids; all
@@ -415,7 +462,7 @@ class SparseMatrix:
         if not isinstance(other, SparseMatrix):
             raise TypeError("%s needs another SparseMatrix, not %r" % (name, type(other).__name__))
         out = [C.c_uint64(0) for _ in range(2 if check else 1)]
-        if getattr(self._lib, "smatrix_" + name)(self._h, other._h, o, *map(int, args), int(max_batch), *map(C.byref, out)) != 0:
+        if getattr(self._lib, "smatrix_" + name)(self._h, other._h, o, *(a if isinstance(a, float) else int(a) for a in args), int(max_batch), *map(C.byref, out)) != 0:
             raise ValueError("smatrix_%s refused: a matrix cannot be merged into itself, and both must be on one device" % name)
         return tuple(v.value for v in out) if check else out[0].value
 
@@ -447,27 +494,32 @@ class SparseMatrix:
         _scale_args(num, den, min_value)
         return self._copy_by(SparseMatrix.merge_scaled, filename, "set", num, den, min_value)
 
-    def merge_topk(self, other, m, op="set", min_value=1, max_batch=0, rank="value"):
+    def merge_topk(self, other, m, op="set", min_value=1, max_batch=0, rank="value", shrink=0.0):
         """merge that keeps the m heaviest pairs of every row of other: of the pairs (y != 0, v >= min_value) those of the largest
         v, equal values by ascending column; the column-0 pair (the CF total) is kept beside them when v >= min_value.  The kept
         pairs are applied as self[x, y] op= v.  1 <= m <= 2**32 - 1.  -> (ops applied, pairs dropped).  other is not modified.
         rank="cosine" (smatrix_merge_topk_by): the m pairs that SCORE best in cf_neighbors_batch / cf_topk_batch /
         cf_recommend_batch, v / (sqrt(other[x, 0]) * sqrt(other[y, 0])) with their guards, equal scores by ascending column;
-        the values applied are still the raw v."""
-        r = _rank(rank)
-        if r == 0:
+        the values applied are still the raw v.
+        rank="jaccard" / "lift", and any scoring rank with shrink > 0 (smatrix_merge_topk_sim): the m pairs that score best in
+        cf_recommend_filtered(sim=rank, shrink=shrink), whose score it is."""
+        rank, h = _rank_args(rank, shrink)
+        if rank == "value":
             return self._merge_call("merge_topk", other, op, m, min_value, check=_topk_args, max_batch=max_batch)
-        return self._merge_call("merge_topk_by", other, op, r, m, min_value, check=_topk_by_args, max_batch=max_batch)
+        if rank == "cosine" and h == 0.0:
+            return self._merge_call("merge_topk_by", other, op, _RANKS[rank], m, min_value, check=_topk_by_args, max_batch=max_batch)
+        return self._merge_call("merge_topk_sim", other, op, _SIMS[rank], h, m, min_value, check=_topk_sim_args, max_batch=max_batch)
 
-    def truncated(self, m, min_value=1, filename=None, rank="value"):
+    def truncated(self, m, min_value=1, filename=None, rank="value", shrink=0.0):
         """a NEW matrix (in memory, or file-backed when filename is given) that holds, of every row of self, the m heaviest pairs
         of at least min_value and the column-0 pair: at most m + 1 pairs per row, the serving copy of an item-kNN recommender
         (total += today; total -= day_30; serving = total.truncated(m)).  self is not modified.
         rank="cosine": the m best-scoring pairs instead of the m heaviest, so that the copy's cf_topk_batch(items, k <= m)
-        returns the scores self's does."""
-        _rank(rank)
+        returns the scores self's does.  rank="jaccard" / "lift" and shrink: as merge_topk -- the copy serves
+        cf_recommend_filtered(sim=rank, shrink=shrink) of one-item sessions, k <= m, as self does."""
+        _rank_args(rank, shrink)
         _topk_args(m, min_value)
-        return self._copy_by(SparseMatrix.merge_topk, filename, m, "set", min_value, 0, rank)
+        return self._copy_by(SparseMatrix.merge_topk, filename, m, "set", min_value, 0, rank, shrink)
 
     def __iadd__(self, other):
         if not isinstance(other, SparseMatrix):
