@@ -190,6 +190,38 @@ int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint6
                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k,
                                  uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
 
+/* The rank of given items in a session's ranking: where a held-out item lands among ALL the session's candidates, not only among
+ * the k <= 64 best -- what hit-rate@k, MRR and the loss of a truncated copy are computed from.  Everything up to and including
+ * shrink is smatrix_cf_recommend_sim's contract, word for word: sessions, first positions, candidates, the score of a pair, weights,
+ * exclusion lists, the deny bitmap, tiers, locks, the mirror, streams, scratch.  There is no k.
+ *   targets    session s asks about targets[t_offsets[s] .. t_offsets[s+1]) (n_sessions + 1 non-decreasing offsets).  A list may
+ *              be empty and may hold an id more than once; every entry is answered on its own: ranks[j] and scores[j] answer
+ *              targets[j].  The targets are looked up, never entered: they change no table, no tier and no other answer.
+ *   answer     when targets[j] is a candidate that is left (the key of a cell in some session item's row, not 0, not an item of
+ *              the session, not on its exclusion list, not denied): scores[j] = its sum, the bytes smatrix_cf_recommend_sim returns
+ *              for it; ranks[j] = the number of candidates left that come before it in the result order (score descending, equal
+ *              scores by ascending id).  So wherever smatrix_cf_recommend_sim with the same arguments returns ids[s*k + r] == t,
+ *              the rank of t is r, and the numbering goes on past 64.  For anything else (the id 0, an id in no scanned row, an
+ *              item of the session, an excluded or denied id): ranks[j] = SMATRIX_RANK_NONE, scores[j] = 0.0.
+ *   n_candidates[s] = the candidates left, uncapped (smatrix_cf_recommend_sim's counts[s] is min(k, this)); written for every
+ *              session, also for one with no targets or no rows.
+ * All three outputs are required, and every entry the call owns is defined when it returns 0.  The host flavour reads and writes
+ * only the entries t_offsets[0] <= j < t_offsets[n_sessions] of targets, ranks and scores (as items from offsets[0]).
+ * Cost: the recommend call's up to the selection, then one pass over the session's table per 64 targets; no sort, no merge.
+ * Returns -1 for smatrix_cf_recommend_sim's refusals but those of k (an unknown sim and a bad shrink in both flavours before the
+ * device is touched, outputs as they were; a bad weight as there: the host flavour before the device is touched, _dev on the device
+ * with the outputs' contents unspecified) and for t_offsets or targets NULL.  0 otherwise, n_sessions == 0 included. */
+#define SMATRIX_RANK_NONE 0xFFFFFFFFu
+int smatrix_cf_rank(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                    const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
+                    double shrink, const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores,
+                    uint32_t* n_candidates);
+int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                        const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                        const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, const uint64_t* d_t_offsets,
+                        const uint32_t* d_targets, uint32_t* d_ranks, double* d_scores, uint32_t* d_n_candidates,
+                        void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

@@ -21,6 +21,9 @@
 // smatrix_cf_recommend_sim (RecFilt::m; k_rec_lds_sim<F>, k_rec_gl_scan_sim<F>: the two kernels that make a score, over the same
 // bodies): the term is kernels/sim.hpp's, the per-row double sqrt(A) or A, the slot's double sqrt(B) or B.  The tiers, the
 // tables and the top-k know nothing of the measure: k_rec_bound, k_rec_gl_init and the rest are the filtered call's.
+// smatrix_cf_rank (RecRank; k_rec_lds_rank<F>, k_rec_lds_rank_sim<F>, k_rec_gl_rank): the same tables with another ending.  Instead
+// of the k best slots, the session's targets are looked up in the finished table (they are never entered: tiers and table sizes
+// are the recommend call's) and the candidates that beat each are counted, rec_rank_table: one pass over the table per 64 targets.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -111,6 +114,84 @@ __device__ __forceinline__ uint32_t rec_find(const uint32_t* keys, uint32_t mask
 }
 __device__ __forceinline__ uint32_t rec_low_word(const double* p) { return *reinterpret_cast<const uint32_t*>(p); }
 
+// what smatrix_cf_rank asks and answers: session s asks about targets[t_off[s] .. t_off[s+1]); ranks / scores run parallel to
+// targets and were filled with SMATRIX_RANK_NONE / 0.0 before the kernels run, so only a target that is found is written
+struct RecRank {
+  const uint64_t* t_off;
+  const uint32_t* targets;
+  uint32_t* ranks;
+  double* scores;
+};
+
+__device__ __forceinline__ long long rec_readlane(long long v, uint32_t j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), (int)j);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// The rank ending of both tiers, run by a workgroup of NW waves over the finished table {keys, sq, sum} of tsize slots (a power of
+// two >= 64) of session s.  A candidate is a slot with key != 0 && sq > 0, the test of the top-k endings; a target is found by
+// probing from its hash until its key or an empty slot (the table is never full), and a found slot that is no candidate is no
+// answer.  Per batch of up to 64 targets: lane j of EVERY wave holds target j's (sum bits, id) and a counter; a wave walks its share
+// of the slots 64 at a time and, for each target of the batch, adds the popcount of the ballot "candidate and better than target
+// j" (CfById's order: the sums are >= +0.0, their bit patterns order as the doubles do) to lane j's counter; the waves' counters
+// are added up through part (NW * 64 + NW words of LDS).  counts[s] = the candidates, counted by the first batch's pass (a session
+// without targets makes that pass alone).
+// FOLDED (the LDS tier, whose 80 KiB leave no LDS for part): the caller has folded the candidate test into the sums -- the sum of
+// a key that is no candidate is -1.0, a sign bit no candidate's sum has -- and sq is not read: part may lie in it.
+template <bool FOLDED, uint32_t NW, typename I>
+__device__ __forceinline__ void rec_rank_table(const uint32_t* keys, const double* sq, const double* sum, I tsize, const RecRank& rk,
+                                               uint32_t s, uint32_t* __restrict__ counts, uint32_t* part) {
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t mask = (uint32_t)(tsize - 1);                      // (a table of 2^32 slots: mask 2^32 - 1)
+  const uint64_t t0 = rk.t_off[s], T = rk.t_off[s + 1] - t0;
+  for (uint64_t j0 = 0; j0 == 0 || j0 < T; j0 += 64) {
+    const uint32_t nt = (uint32_t)(T - j0 < 64 ? T - j0 : 64);
+    const uint32_t b = lane < nt ? rk.targets[t0 + j0 + lane] : 0u;
+    long long tk = NONE;                                            // NONE: no answer (id 0, not in the table, not a candidate)
+    if (b != 0) {
+      uint32_t h = fmix32(b) & mask, c;
+      while ((c = keys[h]) != b && c != 0) h = (h + 1) & mask;
+      if (c == b && (FOLDED || sq[h] > 0.0)) tk = __double_as_longlong(sum[h]);
+      if (tk < 0) tk = NONE;
+    }
+    uint32_t cnt = 0, nc = 0;
+    for (I p0 = w * 64; p0 < tsize; p0 += NW * 64) {
+      const I p = p0 + lane;
+      const uint32_t key = keys[p];
+      long long sk = NONE;
+      if (key != 0 && (FOLDED || sq[p] > 0.0)) sk = __double_as_longlong(sum[p]);
+      const uint64_t cm = __ballot(sk >= 0);                        // the candidates of this step
+      if (cm == 0) continue;
+      nc += (uint32_t)__popcll(cm);
+      for (uint32_t j = 0; j < nt; j++) {                           // (wave-uniform: target j's pair comes as scalars)
+        const long long tj = rec_readlane(tk, j);
+        const uint32_t bj = (uint32_t)__builtin_amdgcn_readlane((int)b, (int)j);
+        const uint64_t m = __ballot(sk > tj || (sk == tj && key < bj)) & cm;
+        if (lane == j) cnt += (uint32_t)__popcll(m);
+      }
+    }
+    part[w * 64 + lane] = cnt;
+    if (lane == 0) part[NW * 64 + w] = nc;
+    __syncthreads();
+    if (w == 0) {
+      uint32_t r = 0;
+      for (uint32_t v = 0; v < NW; v++) r += part[v * 64 + lane];
+      if (lane < nt && tk != NONE) {
+        rk.ranks[t0 + j0 + lane] = r;
+        rk.scores[t0 + j0 + lane] = __longlong_as_double(tk);
+      }
+      if (j0 == 0 && lane == 0) {
+        uint32_t c = 0;
+        for (uint32_t v = 0; v < NW; v++) c += part[NW * 64 + v];
+        counts[s] = c;
+      }
+    }
+    __syncthreads();                                                // before part is written again (or the table cleared)
+  }
+}
+
 // ---- tiers ----------------------------------------------------------------------------------------------------------------
 // bound = the sum of the row sizes (slots) of the session's DISTINCT items: every candidate is a non-empty cell of one of
 // those rows, whatever quirk the row carries.  Duplicates are found exactly for sessions of up to REC_DEDUP_MAX items
@@ -178,13 +259,14 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 }
 
 // ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
-// (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's)
-template <bool F, bool S>
+// (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's; R: smatrix_cf_rank's ending in place
+// of the top-k, k_rec_lds_rank<F> and k_rec_lds_rank_sim<F>: scores and counts are then the targets' and the candidate counts)
+template <bool F, bool S, bool R>
 __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
                                         const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
                                         uint32_t* __restrict__ ids, double* __restrict__ scores, uint32_t* __restrict__ counts,
-                                        const RecFilt& f) {
+                                        const RecFilt& f, const RecRank& rk) {
   __shared__ uint32_t s_key[REC_LDS_SLOTS];
   __shared__ double s_sq[REC_LDS_SLOTS];
   __shared__ double s_sum[REC_LDS_SLOTS];
@@ -257,6 +339,14 @@ __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* a
       __syncthreads();
     }
     __syncthreads();
+    if (R) {
+      // the table fills the LDS two workgroups of a CU share: the candidate test goes into the sums, and s_sq holds the counters
+      for (uint32_t i = tid; i < tsize; i += REC_LDS_THREADS)
+        if (s_key[i] != 0 && !(s_sq[i] > 0.0)) s_sum[i] = -1.0;
+      __syncthreads();
+      rec_rank_table<true, NW>(s_key, s_sq, s_sum, tsize, rk, s, counts, reinterpret_cast<uint32_t*>(s_sq));
+      continue;                                                     // (its last barrier stands before the next session's clearing)
+    }
     // the k best: every wave over its 64-slot steps (k_cf_topk's loop), then wave 0 merges the waves' lists
     CfCand top{NONE, 0xffffffffu, 0xffffffffu};
     for (uint32_t p0 = w * 64; p0 < tsize; p0 += REC_LDS_THREADS) {
@@ -300,7 +390,7 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds(DirSlot* dir, uint3
                                                              const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
                                                              uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
                                                              uint32_t* __restrict__ counts, RecFilt f) {
-  rec_lds<F, false>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f);
+  rec_lds<F, false, false>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{});
 }
 template <bool F>
 __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_sim(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
@@ -308,7 +398,22 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_sim(DirSlot* dir, u
                                                                  const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
                                                                  uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
                                                                  uint32_t* __restrict__ counts, RecFilt f) {
-  rec_lds<F, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f);
+  rec_lds<F, true, false>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{});
+}
+// smatrix_cf_rank's instances: the same fill, rec_rank_table at the end; ncand[s] = the session's candidates
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_rank(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                  const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                  const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                  RecRank rk, uint32_t* __restrict__ ncand, RecFilt f) {
+  rec_lds<F, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, 0u, nullptr, nullptr, ncand, f, rk);
+}
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_rank_sim(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                      const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                      const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                      RecRank rk, uint32_t* __restrict__ ncand, RecFilt f) {
+  rec_lds<F, true, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, 0u, nullptr, nullptr, ncand, f, rk);
 }
 
 // ---- global tier -----------------------------------------------------------------------------------------------------------
@@ -528,5 +633,26 @@ __global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_merge(RecGl R, uin
       if (lane == 0) counts[s] = (uint32_t)__popcll(m);
     }
     __syncthreads();
+  }
+}
+
+// smatrix_cf_rank's ending of the global tier, in place of k_rec_gl_topk + k_rec_gl_merge: a workgroup per session of the group
+__global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_rank(RecGl R, RecRank rk, uint32_t* __restrict__ ncand) {
+  constexpr uint32_t NW = REC_MERGE_THREADS / 64;
+  __shared__ uint32_t part[NW * 64 + NW];
+  for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
+    uint64_t loc;
+    if (!rec_in_group(R, idx, &loc)) continue;
+    const uint32_t s = R.big_list[idx];
+    rec_rank_table<false, NW>(R.gk + loc, R.gq + loc, R.gs + loc, 1ull << R.tlg[s], rk, s, ncand, part);
+  }
+}
+
+// before the kernels above: every answer the call owns reads "no answer" (SMATRIX_RANK_NONE, 0.0)
+__global__ __launch_bounds__(256) void k_rec_rank_fill(uint32_t n, RecRank rk) {
+  const uint64_t j0 = rk.t_off[0], j1 = rk.t_off[n];
+  for (uint64_t j = j0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < j1; j += (uint64_t)gridDim.x * blockDim.x) {
+    rk.ranks[j] = 0xffffffffu;
+    rk.scores[j] = 0.0;
   }
 }

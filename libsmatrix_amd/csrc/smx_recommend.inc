@@ -1,5 +1,5 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
-// smatrix_cf_recommend_filtered / _dev and smatrix_cf_recommend_sim / _dev), host side.
+// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev and smatrix_cf_rank / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -13,6 +13,8 @@
 // with nothing given it runs the <false> ones, the code of smatrix_cf_recommend_batch.
 // The sim call is the filtered call with a measure and a shrinkage in the RecFilt and, for the two kernels that make a score,
 // their _sim instances; with SMATRIX_SIM_COSINE and shrink 0 it IS the filtered call.
+// The rank call is the sim call with another ending (rec_run<.., .., true>): the answers are filled with "no answer", k_rec_lds_rank
+// stands for k_rec_lds, and k_rec_gl_rank for k_rec_gl_topk + k_rec_gl_merge; everything before the ending is shared.
 
 namespace {
 
@@ -32,6 +34,8 @@ struct RecScratch {
   DevBuf<double> h_scores, h_w;                      // ... and the filtered call's: weights, exclusion lists, deny bitmap
   DevBuf<uint64_t> h_exoff;
   DevBuf<uint32_t> h_ex, h_deny;
+  DevBuf<uint64_t> h_toff;                           // ... and the rank call's: target lists, ranks (scores: h_scores, counts: h_counts)
+  DevBuf<uint32_t> h_tg, h_ranks;
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
 };
 
@@ -51,7 +55,7 @@ void rec_trim_all(RecScratch& x, bool all) {
   rec_trim(x.zpos, all); rec_trim(x.cnt, all); rec_trim(x.li, all); rec_trim(x.big_off, all); rec_trim(x.tlg, all); rec_trim(x.gq, all);
   rec_trim(x.gs, all); rec_trim(x.lk, all); rec_trim(x.scan, all); rec_trim(x.part, all); rec_trim(x.h_items, all); rec_trim(x.h_ids, all);
   rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all); rec_trim(x.h_w, all); rec_trim(x.h_exoff, all);
-  rec_trim(x.h_ex, all); rec_trim(x.h_deny, all);
+  rec_trim(x.h_ex, all); rec_trim(x.h_deny, all); rec_trim(x.h_toff, all); rec_trim(x.h_tg, all); rec_trim(x.h_ranks, all);
 }
 
 bool rec_any_big(const RecScratch& x) {
@@ -82,12 +86,15 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
 
 // the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back).
 // F: the filtered call with something given in f; S: the sim call, the score is f.m's.  -1 (nothing but k_rec_bound has run) for
-// a bad weight, 0 otherwise
-template <bool F, bool S>
+// a bad weight, 0 otherwise.
+// R: the ending is the rank call's, not the top-k: rk's answers are filled and written, d_counts receives the candidate counts,
+// k / d_ids / d_scores are not used
+template <bool F, bool S, bool R>
 int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f) {
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, const RecRank& rk) {
   DirSlot* dir = m->d_dir;
   const uint32_t dmask = m->dir_size - 1;
+  if (R) hipLaunchKernelGGL(k_rec_rank_fill, dim3(1024), dim3(256), 0, s, n, rk);
   x.ctl.need(1); x.lds_list.need(n); x.big_list.need(n); x.big_off.need(n); x.tlg.need(n);
   HIP_OK(hipMemsetAsync(x.ctl.p, 0, sizeof(RecCtl), s));
   hipLaunchKernelGGL(k_rec_bound<F>, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, d_off,
@@ -97,7 +104,10 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   HIP_OK(hipMemcpyAsync(&c, x.ctl.p, sizeof c, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   if (F && c.bad) return -1;
-  if (c.n_lds)
+  if (c.n_lds && R)
+    hipLaunchKernelGGL(S ? k_rec_lds_rank_sim<F> : k_rec_lds_rank<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
+                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, rk, d_counts, f);
+  else if (c.n_lds)
     hipLaunchKernelGGL(S ? k_rec_lds_sim<F> : k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
                        x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
   HIP_OK(hipGetLastError());
@@ -106,34 +116,39 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   const uint64_t cap = ngroups == 1 ? c.total_slots : REC_GROUP_SLOTS + c.max_slots;
   const uint64_t nseg = cap / REC_SEG;
   const uint32_t np = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.max_len, REC_PLAN_MAX / c.n_big));
-  x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big); x.lk.need(nseg * 64); x.li.need(nseg * 64);
+  x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big);
+  if (!R) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
   x.cnt.need((uint64_t)np * c.n_big); x.scan.need((uint64_t)np * c.n_big + 1);
-  RecGl R{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
+  RecGl G{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
   for (uint64_t g = 0; g < ngroups; g++) {
-    R.g = (uint32_t)g;
+    G.g = (uint32_t)g;
     const uint64_t ext = ngroups == 1 ? cap : std::min<uint64_t>(cap, c.total_slots - g * REC_GROUP_SLOTS + c.max_slots);
     HIP_OK(hipMemsetAsync(x.gk.p, 0, ext * 4, s));
     HIP_OK(hipMemsetAsync(x.gq.p, 0, ext * 8, s));
     HIP_OK(hipMemsetAsync(x.gs.p, 0, ext * 8, s));
     HIP_OK(hipMemsetAsync(x.owner.p, 0xff, nseg * 4, s));
     HIP_OK(hipMemsetAsync(x.zpos.p, 0, (size_t)c.n_big * 4, s));
-    hipLaunchKernelGGL(k_rec_gl_init<F>, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, R, d_off, d_items, f);
+    hipLaunchKernelGGL(k_rec_gl_init<F>, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, G, d_off, d_items, f);
     HIP_OK(hipGetLastError());
     for (uint32_t p0 = 0; p0 < c.max_len; p0 += np) {
       const uint32_t nj = std::min<uint32_t>(np, c.max_len - p0);
       const uint64_t nt = (uint64_t)nj * c.n_big;
-      hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, R, dir, dmask, d_off, d_items, p0, nj, x.cnt.p);
+      hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, G, dir, dmask, d_off, d_items, p0, nj, x.cnt.p);
       HIP_OK(hipGetLastError());
       rec_scan(x, s, x.cnt.p, nt, x.scan.p);
       for (uint32_t j = 0; j < nj; j++)
-        hipLaunchKernelGGL(S ? k_rec_gl_scan_sim<F> : k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, R, dir, dmask, m->arena.base, d_off,
+        hipLaunchKernelGGL(S ? k_rec_gl_scan_sim<F> : k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, G, dir, dmask, m->arena.base, d_off,
                            d_items, p0, j, x.scan.p, f);
       HIP_OK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, R, nseg, k, x.lk.p,
-                       x.li.p);
-    hipLaunchKernelGGL(k_rec_gl_merge, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, R, k, x.lk.p, x.li.p,
-                       d_ids, d_scores, d_counts);
+    if (R) {
+      hipLaunchKernelGGL(k_rec_gl_rank, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, rk, d_counts);
+    } else {
+      hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, G, nseg, k, x.lk.p,
+                         x.li.p);
+      hipLaunchKernelGGL(k_rec_gl_merge, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, k, x.lk.p, x.li.p,
+                         d_ids, d_scores, d_counts);
+    }
     HIP_OK(hipGetLastError());
   }
   return 0;
@@ -149,13 +164,14 @@ bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_
 bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
 // (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
 
-// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure
+// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending
+template <bool R>
 int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim) {
-  if (sim) return rec_filt_any(f) ? rec_run<true, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f)
-                                  : rec_run<false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f);
-  return rec_filt_any(f) ? rec_run<true, false>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f)
-                         : rec_run<false, false>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f);
+                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim, const RecRank& rk) {
+  if (sim) return rec_filt_any(f) ? rec_run<true, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
+                                  : rec_run<false, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
+  return rec_filt_any(f) ? rec_run<true, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
+                         : rec_run<false, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
 }
 
 // smatrix_cf_recommend_filtered_dev and smatrix_cf_recommend_sim_dev behind their refusals; sim: score by f_m, not by the cosine
@@ -171,7 +187,7 @@ int rec_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offse
   RecScratch& x = rec_of(m);
   rec_begin(x, s);
   const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, f_m};
-  const int rc = rec_dispatch(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim);
+  const int rc = rec_dispatch<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, RecRank{});
   rec_end(x, s);
   if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
   rec_trim_all(x, false);
@@ -221,7 +237,7 @@ int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offset
   }
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as smatrix_cf_recommend_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_dispatch(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim);
+  rec_dispatch<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{});
   HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
@@ -229,6 +245,87 @@ int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offset
   HIP_OK(hipStreamSynchronize(s));
   rec_trim_all(x, false);
   return 0;
+}
+
+// smatrix_cf_rank_dev behind its refusals: rec_filtered_dev with the rank ending
+int rec_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
+                 const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, bool sim,
+                 SimArgs f_m, const RecRank& rk, uint32_t* d_n_candidates, void* hip_stream) {
+  if (n_sessions == 0) return 0;
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, f_m};
+  const int rc = rec_dispatch<true>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, 0u, nullptr, nullptr, d_n_candidates, f, sim, rk);
+  rec_end(x, s);
+  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
+  rec_trim_all(x, false);
+  return rc;
+}
+
+// the host flavour: rec_filtered_host's copies, and the target lists and the answers' [t_offsets[0], t_offsets[n]) beside them
+int rec_rank_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                  const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, bool sim, SimArgs f_m,
+                  const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores, uint32_t* n_candidates) {
+  if (n_sessions == 0) return 0;
+  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0], n_t = t_offsets[n] - t_offsets[0];
+  if (weights)
+    for (uint64_t i = 0; i < n_items; i++)
+      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
+  Matrix* m = M(self);
+  set_device(m);
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, false);
+  hipStream_t s = m->stream;
+  RecScratch& x = rec_of(m);
+  rec_begin(x, s);
+  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
+  std::vector<uint64_t> rel(n + 1), t_rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
+  for (uint64_t i = 0; i <= n; i++) { rel[i] = offsets[i] - offsets[0]; t_rel[i] = t_offsets[i] - t_offsets[0]; }
+  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
+  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_counts.need(n);
+  x.h_toff.need(n + 1); x.h_tg.need(std::max<uint64_t>(n_t, 1)); x.h_ranks.need(std::max<uint64_t>(n_t, 1)); x.h_scores.need(std::max<uint64_t>(n_t, 1));
+  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(x.h_toff.p, t_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (n_t) HIP_OK(hipMemcpyAsync(x.h_tg.p, targets + t_offsets[0], n_t * 4, hipMemcpyHostToDevice, s));
+  RecFilt f{};
+  f.m = f_m;
+  if (weights) {
+    x.h_w.need(std::max<uint64_t>(n_items, 1));
+    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
+    f.w = x.h_w.p;
+  }
+  if (ex_offsets) {
+    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
+    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
+    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
+  }
+  if (deny_n) {
+    x.h_deny.need(n_deny);
+    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
+    f.deny = x.h_deny.p; f.deny_n = deny_n;
+  }
+  const RecRank rk{x.h_toff.p, x.h_tg.p, x.h_ranks.p, x.h_scores.p};
+  rec_dispatch<true>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, 0u, nullptr, nullptr, x.h_counts.p, f, sim, rk);
+  HIP_OK(hipMemcpyAsync(n_candidates, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
+  if (n_t) HIP_OK(hipMemcpyAsync(ranks + t_offsets[0], x.h_ranks.p, n_t * 4, hipMemcpyDeviceToHost, s));
+  if (n_t) HIP_OK(hipMemcpyAsync(scores + t_offsets[0], x.h_scores.p, n_t * 8, hipMemcpyDeviceToHost, s));
+  rec_end(x, s);
+  HIP_OK(hipStreamSynchronize(s));
+  rec_trim_all(x, false);
+  return 0;
+}
+
+// what both flavours of the rank call refuse before anything else (k: there is none)
+bool rec_rank_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n, int sim,
+                      double shrink, const void* t_offsets, const void* targets) {
+  return sim_args_ok(sim, shrink) && rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, 1u) && t_offsets && targets;
 }
 
 void recommend_release(Matrix* m) {
@@ -255,7 +352,7 @@ int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uin
   hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
   RecScratch& x = rec_of(m);
   rec_begin(x, s);
-  rec_run<false, false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{});
+  rec_run<false, false, false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{}, RecRank{});
   rec_end(x, s);
   if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
   rec_trim_all(x, false);
@@ -281,7 +378,7 @@ int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_
   if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as cf_topk_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_run<false, false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{});
+  rec_run<false, false, false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{}, RecRank{});
   HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
@@ -324,6 +421,25 @@ int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t*
   if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
   return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
                            !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
+}
+
+int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
+                        const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, int sim,
+                        double shrink, const uint64_t* d_t_offsets, const uint32_t* d_targets, uint32_t* d_ranks, double* d_scores,
+                        uint32_t* d_n_candidates, void* hip_stream) {
+  if (!rec_rank_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink, d_t_offsets, d_targets)) return -1;
+  return rec_rank_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n,
+                      !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, RecRank{d_t_offsets, d_targets, d_ranks, d_scores},
+                      d_n_candidates, hip_stream);
+}
+
+int smatrix_cf_rank(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                    const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
+                    double shrink, const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores,
+                    uint32_t* n_candidates) {
+  if (!rec_rank_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink, t_offsets, targets)) return -1;
+  return rec_rank_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n,
+                       !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, t_offsets, targets, ranks, scores, n_candidates);
 }
 
 }  // extern "C"

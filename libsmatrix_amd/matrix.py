@@ -100,6 +100,21 @@ def _topk_sim_args(sim, shrink, m, min_value):
     _topk_args(m, min_value)
 
 
+RANK_NONE = 0xFFFFFFFF                                   # SMATRIX_RANK_NONE: the rank of a target that is no candidate
+
+
+def rank_metrics(ranks, ks=(1, 10, 100)):
+    """ranks as cf_rank returns them -> {"n": targets, "found": those with a rank, "hit_rate": {k: share with rank < k},
+    "mrr": mean of 1 / (rank + 1), a target without a rank counting 0}; every share of an empty input is 0.0"""
+    r = np.asarray(ranks, dtype=np.uint32).ravel().astype(np.int64)
+    found = r != RANK_NONE
+    n = int(r.size)
+    rr = np.where(found, 1.0 / (r.astype(np.float64) + 1.0), 0.0)
+    return {"n": n, "found": int(np.count_nonzero(found)),
+            "hit_rate": {int(k): (float(np.count_nonzero(found & (r < int(k)))) / n if n else 0.0) for k in ks},
+            "mrr": float(rr.sum() / n) if n else 0.0}
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -365,6 +380,72 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_sim_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
                                                   deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_sim_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
+
+    def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """where given items land in each session's ranking (include/smatrix_batch.h smatrix_cf_rank): cf_recommend_filtered's
+        arguments without k, and targets, one id sequence per session (it may be empty or repeat an id).
+        -> (ranks uint32[T], scores float64[T], n_candidates uint32[n]), the T answers concatenated in session order: the rank of
+        a target is the number of the session's candidates that come before it (the position cf_recommend_filtered would give it,
+        numbered on past 64) and its score the one returned there; RANK_NONE and 0.0 for a target that is no candidate (the id 0,
+        an id in no scanned row, an item of the session, an excluded or denied id).  n_candidates is uncapped"""
+        code, h = _sim(sim), _shrink(shrink)
+        n = len(sessions)
+        w = None if weights is None else _weights(weights, sessions)
+        if len(targets) != n:
+            raise ValueError("targets must hold one id sequence per session")
+        if exclude is not None and len(exclude) != n:
+            raise ValueError("exclude must hold one id sequence per session")
+        offsets, items = _sessions(sessions)
+        t_off, tg = _sessions(targets)
+        ex_off, ex = _sessions(exclude) if exclude is not None else (None, None)
+        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        ranks = np.full(tg.size, RANK_NONE, dtype=np.uint32)
+        scores = np.zeros(tg.size, dtype=np.float64)
+        ncand = np.zeros(n, dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        if n and self._lib.smatrix_cf_rank(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
+                                           None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
+                                           None if bits is None else _p(bits), deny_n, code, h, t_off.ctypes.data_as(_lib.u64p), _p(tg),
+                                           _p(ranks), scores.ctypes.data_as(dp), _p(ncand)) != 0:
+            raise ValueError("smatrix_cf_rank: bad n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
+        return ranks, scores, ncand
+
+    def cf_rank_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, t_off_ptr,
+                    targets_ptr, ranks_ptr, scores_ptr, ncand_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for a filter that is not given): cf_recommend_sim_dev's inputs, and
+        t_off uint64[n+1], targets uint32, ranks uint32 and scores float64 parallel to targets, ncand uint32[n]"""
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_rank_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, code, h,
+                                         t_off_ptr, targets_ptr, ranks_ptr, scores_ptr, ncand_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_rank_dev: bad n, weights, exclusion lists, deny bitmap, sim, shrink or targets")
+
+    def cf_evaluate(self, sessions, ks=(1, 10, 100), **measure):
+        """held-out evaluation of the read path's dials: of every session with at least two distinct ids the LAST id is hidden
+        and ranked (cf_rank) against the rest of the session, the hidden id's other occurrences removed from it; -> rank_metrics
+        of those ranks (hit rate at each k of ks, MRR).  measure: cf_rank's weights (shaped like sessions: a removed position's
+        weight goes with it), exclude, deny, sim, shrink.
+        Caveat (leave-one-out): sessions that are already counted in the matrix flatter the result -- the hidden id's
+        co-occurrence with the rest of its session is in the very counts it is ranked by.  Evaluate with sessions that were not
+        imported"""
+        weights, exclude = measure.pop("weights", None), measure.pop("exclude", None)
+        if weights is not None and (len(weights) != len(sessions) or any(len(w) != len(s) for w, s in zip(weights, sessions))):
+            raise ValueError("weights must hold one sequence per session, of the session's length")
+        if exclude is not None and len(exclude) != len(sessions):
+            raise ValueError("exclude must hold one id sequence per session")
+        q, tg, qw, qe = [], [], [], []
+        for i, s in enumerate(sessions):
+            s = np.asarray(s, dtype=np.uint32)
+            if np.unique(s).size < 2:
+                continue
+            keep = s != s[-1]
+            q.append(s[keep]); tg.append(s[-1:])
+            if weights is not None:
+                qw.append(np.asarray(weights[i], dtype=np.float64)[keep])
+            if exclude is not None:
+                qe.append(exclude[i])
+        ranks, _, _ = self.cf_rank(q, tg, weights=qw if weights is not None else None, exclude=qe if exclude is not None else None, **measure)
+        return rank_metrics(ranks, ks)
 
     def cf_import_sessions(self, sessions):
         """CF-recommender write path (examples/cf_recommender.c:36-47): every session is a sequence of item ids; all
