@@ -222,6 +222,55 @@ int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_of
                         const uint32_t* d_targets, uint32_t* d_ranks, double* d_scores, uint32_t* d_n_candidates,
                         void* hip_stream);
 
+/* Why an item was recommended: each session item's share of a candidate's score ("because you viewed X and Y").  A score of
+ * smatrix_cf_recommend_sim is a left-to-right sum of w_a * score(a, b) over the session's distinct items; this call returns the
+ * terms of that sum for the targets the caller names, one per (target, session position), made by the library's own rules.
+ * Sessions, weights, sim and shrink are smatrix_cf_recommend_sim's, word for word; targets and t_offsets are smatrix_cf_rank's (a
+ * list may be empty and may hold an id more than once; every entry is answered on its own).  L_s = the length of session s, T_s =
+ * the number of its targets.
+ *   layout     dense, one entry per (target, position): E_s = the sum of T_s' * L_s' over the sessions before s; target number j
+ *              of session s (counted from 0 within the session) and position i < L_s own entry E_s + j * L_s + i of terms and of
+ *              cc, so session s's block reshapes to (T_s, L_s).  The host flavour computes E_s itself and writes
+ *              terms[0 .. E_n) and cc[0 .. E_n); it reads items, weights and targets from offsets[0] and t_offsets[0] on, as
+ *              smatrix_cf_rank does.  _dev: the caller passes d_e_offsets (n_sessions + 1 entries, d_e_offsets[s] = E_s) and
+ *              total = E_n (as d_op_offsets / total_ops of smatrix_cf_import_sessions_dev).  The kernels write nothing outside
+ *              [0, total) of the two outputs whatever d_e_offsets holds; with offsets that are not the E_s above the contents are
+ *              unspecified.
+ *   answer     for target t and position i holding item a.  terms = +0.0 and cc = 0 when t == 0, when a occurs earlier in the
+ *              session (first positions count, exactly, at every session length), when a has no row, or when a's row has no
+ *              cell with key t.  Otherwise cc = what smatrix_get(a, t) returns, and terms = w * score: score is
+ *              smatrix_cf_recommend_sim's score of the pair (t, cc) in row a for (sim, shrink) -- ta == 0 scores 0, tb == 0
+ *              counts as 1, base rounded on its own before shrink is added --, w the weight at that position (1.0 with weights
+ *              NULL), the product rounded to double on its own.  A weight of -0.0 acts as 0.0: no entry is ever -0.0.  A dead
+ *              cell (cc == 0) gives +0.0.
+ *   no filters there is no exclusion list and no deny bitmap: an explanation does not depend on whether t would be served, and a
+ *              target that is itself an item of the session is answered like any other.
+ * What ties it to the rest: wherever smatrix_cf_rank with the same sessions, weights, sim and shrink (and any filters) answers
+ * target t of session s with a rank, the left-to-right sum from 0.0 of that target's L_s terms has exactly the bytes of its
+ * scores[j] -- the bytes of smatrix_cf_recommend_sim's score for t.  One exception: a row that holds a key twice (SURVEY.md quirk
+ * Q4, a reloaded file); the recommend call adds both cells' terms, this call reports the cell smatrix_get finds.
+ * Cost: sum of T_s * L_s look-ups, one per entry, after a pre-pass of one look-up per session entry and one per target.  The
+ * pre-pass finds the first positions by the quadratic wave compare of smatrix_cf_recommend_batch's tier pass (every position
+ * against all earlier ones, 64 at a time: L_s * (L_s + 1) / 2 compares), here without its cut at 8192 ids.  Scratch: 8 bytes per
+ * session entry and 8 bytes per target; the host flavour also holds device copies of its inputs and outputs for the call.  No
+ * session table is built.  _dev reads d_offsets[n_sessions] and d_t_offsets[n_sessions] back (16 bytes) to size the scratch.
+ * Locks, the mirror and streams are smatrix_cf_rank's: the matrix lock for the call, scalar writes still in the host mirror
+ * written back first, the scratch ordered behind the previous read-path call whatever its stream, hip_stream == NULL
+ * synchronises; file-backed matrices work unchanged.  The matrix is not modified.  Deterministic: the same contents and input give
+ * the same bytes.
+ * Returns -1 for n_sessions >= 2^32, an unknown sim, a shrink that is negative, NaN or infinite (both flavours, before the device
+ * is touched, outputs as they were), t_offsets, targets, terms or cc NULL, _dev: d_e_offsets NULL, and a weight that is negative,
+ * NaN or infinite: the host flavour checks the weights before it touches the device and leaves the outputs as they were, _dev
+ * finds them on the device (one 4-byte read-back) and leaves the outputs' contents unspecified.  0 otherwise, n_sessions == 0 and
+ * total == 0 included. */
+int smatrix_cf_explain(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                       int sim, double shrink, const uint64_t* t_offsets, const uint32_t* targets,
+                       double* terms, uint32_t* cc);
+int smatrix_cf_explain_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                           const double* d_weights, int sim, double shrink, const uint64_t* d_t_offsets,
+                           const uint32_t* d_targets, const uint64_t* d_e_offsets, uint64_t total,
+                           double* d_terms, uint32_t* d_cc, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

@@ -82,6 +82,9 @@ def load():
         "smatrix_cf_rank": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64, C.c_int, C.c_double,
                                       u64p, u32p, u32p, C.POINTER(C.c_double), u32p]),
         "smatrix_cf_rank_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, C.c_int, C.c_double, V, V, V, V, V, V]),
+        "smatrix_cf_explain": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), C.c_int, C.c_double, u64p, u32p,
+                                         C.POINTER(C.c_double), u32p]),
+        "smatrix_cf_explain_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_int, C.c_double, V, V, V, C.c_uint64, V, V, V]),
         "smatrix_cf_import_sessions": (C.c_int, [H, C.c_size_t, u64p, u32p]),
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
         "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),

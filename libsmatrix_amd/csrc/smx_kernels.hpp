@@ -36,6 +36,7 @@ namespace smx {
 #include "kernels/sim.hpp"
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
+#include "kernels/explain.hpp"
 #include "kernels/io_router.hpp"
 #include "kernels/probes.hpp"
 

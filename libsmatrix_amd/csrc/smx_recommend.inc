@@ -36,6 +36,8 @@ struct RecScratch {
   DevBuf<uint32_t> h_ex, h_deny;
   DevBuf<uint64_t> h_toff;                           // ... and the rank call's: target lists, ranks (scores: h_scores, counts: h_counts)
   DevBuf<uint32_t> h_tg, h_ranks;
+  DevBuf<uint64_t> h_eoff;                           // ... and the explain call's (smx_explain.inc): entry offsets (terms: h_scores, cc: h_ids),
+  DevBuf<double> e_ra, e_cb;                         // and both its flavours' doubles per session entry and per target
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
 };
 
@@ -56,6 +58,7 @@ void rec_trim_all(RecScratch& x, bool all) {
   rec_trim(x.gs, all); rec_trim(x.lk, all); rec_trim(x.scan, all); rec_trim(x.part, all); rec_trim(x.h_items, all); rec_trim(x.h_ids, all);
   rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all); rec_trim(x.h_w, all); rec_trim(x.h_exoff, all);
   rec_trim(x.h_ex, all); rec_trim(x.h_deny, all); rec_trim(x.h_toff, all); rec_trim(x.h_tg, all); rec_trim(x.h_ranks, all);
+  rec_trim(x.h_eoff, all); rec_trim(x.e_ra, all); rec_trim(x.e_cb, all);
 }
 
 bool rec_any_big(const RecScratch& x) {

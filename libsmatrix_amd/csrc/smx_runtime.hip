@@ -3425,5 +3425,8 @@ void smx_stream_release_device(smx_stream_t* st) {
 // ---- session recommendations (include/smatrix_batch.h) ------------------------------------------
 #include "smx_recommend.inc"
 
+// ---- each session item's share of a candidate's score (smatrix_cf_explain) ------------------------
+#include "smx_explain.inc"
+
 // ---- the multi-GPU router (include/smatrix_shard.h) ---------------------------------------------------
 #include "smx_shard.inc"

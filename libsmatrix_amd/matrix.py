@@ -115,6 +115,25 @@ def rank_metrics(ranks, ks=(1, 10, 100)):
             "mrr": float(rr.sum() / n) if n else 0.0}
 
 
+def explain_table(sessions, targets, terms, cc, e_offsets, top=None):
+    """what cf_explain returns, as something to show: per session a list with one entry per target, each a list of
+    (item, cc, term) tuples -- the session's items that put the target where it is, by term descending, equal terms by ascending
+    position; entries with cc == 0 (the item's row does not hold the target, or a later occurrence of the item) are left out; cut
+    at `top` entries when given.  Pure numpy, no library call"""
+    terms, cc = np.asarray(terms, dtype=np.float64).ravel(), np.asarray(cc, dtype=np.uint32).ravel()
+    out = []
+    for s, (sess, tg) in enumerate(zip(sessions, targets)):
+        items, L, e0 = np.asarray(sess, dtype=np.uint32), len(sess), int(e_offsets[s])
+        rows = []
+        for j in range(len(tg)):
+            t, c = terms[e0 + j * L:e0 + (j + 1) * L], cc[e0 + j * L:e0 + (j + 1) * L]
+            at = np.flatnonzero(c != 0)
+            at = at[np.argsort(-t[at], kind="stable")][:top]
+            rows.append([(int(items[i]), int(c[i]), float(t[i])) for i in at])
+        out.append(rows)
+    return out
+
+
 def _sessions(sessions):
     """a list of id sequences -> (offsets uint64[n+1], ids uint32[total])"""
     lens = np.array([len(s) for s in sessions], dtype=np.uint64)
@@ -419,6 +438,51 @@ class SparseMatrix:
         if self._lib.smatrix_cf_rank_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, code, h,
                                          t_off_ptr, targets_ptr, ranks_ptr, scores_ptr, ncand_ptr, sp) != 0:
             raise ValueError("smatrix_cf_rank_dev: bad n, weights, exclusion lists, deny bitmap, sim, shrink or targets")
+
+    def cf_explain(self, sessions, targets, weights=None, sim="cosine", shrink=0.0):
+        """each session item's share of a target's score (include/smatrix_batch.h smatrix_cf_explain): sessions, weights, sim and
+        shrink as cf_recommend_filtered takes them, targets one id sequence per session (it may be empty or repeat an id); no
+        filters.  -> (terms float64[E], cc uint32[E], e_offsets uint64[n + 1]): session s's block terms[e_offsets[s]:e_offsets[s + 1]]
+        reshapes to (its targets, its length); the entry of target t and the position holding item a is w * score(a, t) and
+        self[a, t], or 0.0 and 0 when t is 0, a occurred earlier in the session, or a's row does not hold t.  Added left to right,
+        a target's terms give the bytes of the score cf_recommend_filtered and cf_rank return for it; explain_table turns the
+        arrays into sorted (item, cc, term) lists"""
+        code, h = _sim(sim), _shrink(shrink)
+        n = len(sessions)
+        w = None if weights is None else _weights(weights, sessions)
+        if len(targets) != n:
+            raise ValueError("targets must hold one id sequence per session")
+        offsets, items = _sessions(sessions)
+        t_off, tg = _sessions(targets)
+        e_off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(np.diff(offsets) * np.diff(t_off), out=e_off[1:])
+        terms = np.zeros(int(e_off[-1]), dtype=np.float64)
+        cc = np.zeros(int(e_off[-1]), dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        if n and self._lib.smatrix_cf_explain(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
+                                              code, h, t_off.ctypes.data_as(_lib.u64p), _p(tg), terms.ctypes.data_as(dp), _p(cc)) != 0:
+            raise ValueError("smatrix_cf_explain: bad n_sessions, weights, sim or shrink")
+        return terms, cc, e_off
+
+    def cf_explain_dev(self, n, off_ptr, items_ptr, weights_ptr, sim, shrink, t_off_ptr, targets_ptr, e_off_ptr, total, terms_ptr,
+                       cc_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for no weights): off uint64[n+1], items uint32, weights float64 per item,
+        t_off uint64[n+1], targets uint32, e_off uint64[n+1] (e_off[s] = the sum of targets * length over the sessions before s),
+        total = e_off[n], terms float64[total], cc uint32[total].  A bad weight is found on the device: ValueError, the outputs'
+        contents unspecified"""
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_explain_dev(self._h, n, off_ptr, items_ptr, weights_ptr, code, h, t_off_ptr, targets_ptr, e_off_ptr, total,
+                                            terms_ptr, cc_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_explain_dev: bad n, weights, sim, shrink, targets or entry offsets")
+
+    def cf_recommend_explained(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_filtered, and cf_explain for what it returned: each session's k returned ids are its targets (unused
+        slots hold the id 0 and explain to zeros).  -> (ids[n,k], scores[n,k], counts[n], terms, cc, e_offsets): session s's block
+        of terms and cc reshapes to (k, its length)"""
+        ids, scores, counts = self.cf_recommend_filtered(sessions, k, weights=weights, exclude=exclude, deny=deny, sim=sim, shrink=shrink)
+        terms, cc, e_off = self.cf_explain(sessions, list(ids), weights=weights, sim=sim, shrink=shrink)
+        return ids, scores, counts, terms, cc, e_off
 
     def cf_evaluate(self, sessions, ks=(1, 10, 100), **measure):
         """held-out evaluation of the read path's dials: of every session with at least two distinct ids the LAST id is hidden
