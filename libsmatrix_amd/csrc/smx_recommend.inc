@@ -3,14 +3,21 @@
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
-// Under the matrix lock, after the scalar mirror has been written back (cache_sync):
-//   1. k_rec_bound sorts the sessions into the LDS tier and the global tier; ONE read-back of RecCtl (counts, global-tier sizes)
-//   2. k_rec_lds: every LDS-tier session, one workgroup each
-//   3. the global tier, per group of sessions whose tables fit REC_GROUP_SLOTS (normally one group): zeroed tables, k_rec_gl_init,
-//      per block of item positions the chunk counts (k_rec_gl_plan) and their scan, a k_rec_gl_scan launch per position (the
-//      kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
-// The filtered call is the same driver with a RecFilt (weights, exclusion lists, deny bitmap) and the kernels' <true> instances;
-// with nothing given it runs the <false> ones, the code of smatrix_cf_recommend_batch.
+// Three layers, top down:
+//   the extern "C" symbols   refuse bad arguments, then name what the call was given: a RecFilt, a measure, a RecRank
+//   RecCall                  ONE scope for every call on the read path's scratch (smx_explain.inc's two as well): the matrix lock,
+//                            the scalar mirror written back (cache_sync), the stream, the wait for the call before, and at finish
+//                            the event, the synchronisation rule and the trim.  Its stagers carry a host flavour's arrays to the
+//                            device: stage (a window of a list of lists: sessions, exclusion lists, targets), stage_weights,
+//                            stage_filter.  A _dev flavour is the scope around the driver; a host flavour stages, runs, copies back
+//   rec_run<F, S, R>         the driver, every array on the device:
+//     1. k_rec_bound sorts the sessions into the LDS tier and the global tier; ONE read-back of RecCtl (counts, global-tier sizes)
+//     2. k_rec_lds: every LDS-tier session, one workgroup each
+//     3. the global tier, per group of sessions whose tables fit REC_GROUP_SLOTS (normally one group): zeroed tables, k_rec_gl_init,
+//        per block of item positions the chunk counts (k_rec_gl_plan) and their scan, a k_rec_gl_scan launch per position (the
+//        kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
+// The filtered call runs the kernels' <true> instances for its RecFilt (weights, exclusion lists, deny bitmap); with nothing given
+// it runs the <false> ones, and that is what smatrix_cf_recommend_batch is: the filtered call with nothing given.
 // The sim call is the filtered call with a measure and a shrinkage in the RecFilt and, for the two kernels that make a score,
 // their _sim instances; with SMATRIX_SIM_COSINE and shrink 0 it IS the filtered call.
 // The rank call is the sim call with another ending (rec_run<.., .., true>): the answers are filled with "no answer", k_rec_lds_rank
@@ -39,6 +46,13 @@ struct RecScratch {
   DevBuf<uint64_t> h_eoff;                           // ... and the explain call's (smx_explain.inc): entry offsets (terms: h_scores, cc: h_ids),
   DevBuf<double> e_ra, e_cb;                         // and both its flavours' doubles per session entry and per target
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
+  // EVERY buffer above, and the only list of them: the trim, the "any buffer big" test and the release are this visitor's
+  template <typename Fn>
+  void for_each_buf(Fn f) {
+    f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
+    f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
+    f(h_eoff); f(e_ra); f(e_cb);
+  }
 };
 
 RecScratch& rec_of(Matrix* m) {
@@ -48,33 +62,104 @@ RecScratch& rec_of(Matrix* m) {
 
 template <typename T>
 bool rec_big(const DevBuf<T>& b) { return b.cap * sizeof(T) > ((size_t)64 << 20); }
-template <typename T>
-void rec_trim(DevBuf<T>& b, bool all) {
-  if (all || rec_big(b)) b.release();                                 // (as the export: no HBM pinned for good)
-}
 void rec_trim_all(RecScratch& x, bool all) {
-  rec_trim(x.ctl, all); rec_trim(x.lds_list, all); rec_trim(x.big_list, all); rec_trim(x.gk, all); rec_trim(x.owner, all);
-  rec_trim(x.zpos, all); rec_trim(x.cnt, all); rec_trim(x.li, all); rec_trim(x.big_off, all); rec_trim(x.tlg, all); rec_trim(x.gq, all);
-  rec_trim(x.gs, all); rec_trim(x.lk, all); rec_trim(x.scan, all); rec_trim(x.part, all); rec_trim(x.h_items, all); rec_trim(x.h_ids, all);
-  rec_trim(x.h_counts, all); rec_trim(x.h_off, all); rec_trim(x.h_scores, all); rec_trim(x.h_w, all); rec_trim(x.h_exoff, all);
-  rec_trim(x.h_ex, all); rec_trim(x.h_deny, all); rec_trim(x.h_toff, all); rec_trim(x.h_tg, all); rec_trim(x.h_ranks, all);
-  rec_trim(x.h_eoff, all); rec_trim(x.e_ra, all); rec_trim(x.e_cb, all);
+  x.for_each_buf([all](auto& b) { if (all || rec_big(b)) b.release(); });   // (as the export: no HBM pinned for good)
+}
+bool rec_any_big(RecScratch& x) {
+  bool big = false;
+  x.for_each_buf([&big](auto& b) { big = big || rec_big(b); });
+  return big;
 }
 
-bool rec_any_big(const RecScratch& x) {
-  return rec_big(x.lds_list) || rec_big(x.big_list) || rec_big(x.gk) || rec_big(x.owner) || rec_big(x.zpos) || rec_big(x.cnt) ||
-         rec_big(x.li) || rec_big(x.big_off) || rec_big(x.tlg) || rec_big(x.gq) || rec_big(x.gs) || rec_big(x.lk) || rec_big(x.scan) ||
-         rec_big(x.part);
-}
+// a window of a caller's list of lists on the device: offsets that start at 0, the values they name, and how many those are
+struct RecList {
+  const uint64_t* off;
+  const uint32_t* val;
+  uint64_t count;
+};
 
-// The scratch is the matrix's, the stream the caller's: a call on another stream than the one before it (or the host flavour,
-// on the matrix's stream) must not touch the scratch while kernels of the earlier call may still read it.
-void rec_begin(RecScratch& x, hipStream_t s) {
-  if (x.done) HIP_OK(hipStreamWaitEvent(s, x.done, 0));
-}
-void rec_end(RecScratch& x, hipStream_t s) {
-  if (!x.done) HIP_OK(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(x.done, s));
+// One call on the read path's scratch, from the lock to the trim; every entry point opens one behind its refusals.
+// The scratch is the matrix's, the stream the caller's: a call on another stream than the one before it (or a host flavour, on
+// the matrix's stream) must not touch the scratch while kernels of the earlier call may still read it -- hence `done`.
+struct RecCall {
+  Matrix* const m;
+  std::unique_lock<std::mutex> lock;
+  hipStream_t s;
+  RecScratch* scratch;
+  const bool host;                                        // a host flavour: finish always synchronises
+  std::vector<std::vector<uint64_t>> rel;                 // the offsets the copies in flight read: alive until finish
+
+  explicit RecCall(smatrix_t* self) : RecCall(self, true, nullptr) {}                      // a host flavour: the matrix's stream
+  RecCall(smatrix_t* self, void* hip_stream) : RecCall(self, false, hip_stream) {}         // a _dev flavour: NULL = the legacy default stream
+  RecCall(smatrix_t* self, bool host_flavour, void* hip_stream) : m(M(self)), host(host_flavour) {
+    set_device(m);
+    lock = std::unique_lock<std::mutex>(m->mu);
+    cache_sync(m, false);
+    s = host ? m->stream : static_cast<hipStream_t>(hip_stream);
+    scratch = &rec_of(m);
+    if (scratch->done) HIP_OK(hipStreamWaitEvent(s, scratch->done, 0));
+  }
+  RecScratch& x() { return *scratch; }
+
+  // The end of the call, whatever it returns.  The kernels use the buffers the trim releases, so a _dev call whose stream is the
+  // caller's returns with its work in flight only when no buffer is above the threshold.  The test runs over ALL buffers: one
+  // that is big now was grown by this call, because the call that made a buffer big before synchronised and released it here.
+  int finish(int rc) {
+    RecScratch& x = *scratch;
+    if (!x.done) HIP_OK(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(x.done, s));
+    if (host || !s || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));
+    rec_trim_all(x, false);
+    return rc;
+  }
+
+  // offsets[0 .. n] and values[offsets[0] .. offsets[n]) of the caller: zero-based offsets to d_off, the values to d_val (sized to
+  // one element when there is none: no NULL goes to a kernel)
+  RecList stage(uint64_t n, const uint64_t* offsets, const uint32_t* values, DevBuf<uint64_t>& d_off, DevBuf<uint32_t>& d_val) {
+    rel.emplace_back(n + 1);
+    std::vector<uint64_t>& r = rel.back();
+    for (uint64_t i = 0; i <= n; i++) r[i] = offsets[i] - offsets[0];
+    d_off.need(n + 1); d_val.need(std::max<uint64_t>(r[n], 1));
+    HIP_OK(hipMemcpyAsync(d_off.p, r.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (r[n]) HIP_OK(hipMemcpyAsync(d_val.p, values + offsets[0], r[n] * 4, hipMemcpyHostToDevice, s));
+    return RecList{d_off.p, d_val.p, r[n]};
+  }
+  // the weights of the staged sessions (they lie at the sessions' offsets), or NULL for none
+  const double* stage_weights(const double* weights, uint64_t first, uint64_t n_items) {
+    if (!weights) return nullptr;
+    RecScratch& x = *scratch;
+    x.h_w.need(std::max<uint64_t>(n_items, 1));
+    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + first, n_items * 8, hipMemcpyHostToDevice, s));
+    return x.h_w.p;
+  }
+  // a host flavour's RecFilt: the weights, the exclusion lists and the deny bitmap, whichever were given
+  RecFilt stage_filter(uint64_t n, const uint64_t* offsets, const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                       const uint32_t* deny_bits, uint64_t deny_n, SimArgs f_m) {
+    RecScratch& x = *scratch;
+    RecFilt f{};
+    f.m = f_m;
+    f.w = stage_weights(weights, offsets[0], offsets[n] - offsets[0]);
+    if (ex_offsets) {
+      const RecList ex = stage(n, ex_offsets, ex_items, x.h_exoff, x.h_ex);
+      f.ex_off = ex.off; f.ex = ex.val;
+    }
+    if (deny_n) {
+      const uint64_t n_deny = (deny_n + 31) / 32;
+      x.h_deny.need(n_deny);
+      HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
+      f.deny = x.h_deny.p; f.deny_n = deny_n;
+    }
+    return f;
+  }
+};
+
+// a host flavour's weights, before the device is touched: the sessions' entries finite and >= 0 (the _dev flavours find a bad
+// one on the device)
+bool rec_host_weights_ok(const double* weights, const uint64_t* offsets, uint64_t n) {
+  if (weights)
+    for (uint64_t i = offsets[0]; i < offsets[n]; i++)
+      if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) return false;
+  return true;
 }
 
 // out[0 .. n] = exclusive prefix of n u32 counts (the export's scan kernels)
@@ -157,10 +242,11 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   return 0;
 }
 
-// what both flavours of the filtered call refuse before anything else
+// what both flavours of the plain call refuse, and of the filtered call before anything else
+bool rec_k_ok(size_t n_sessions, uint32_t k) { return k != 0 && k <= 64 && n_sessions <= 0xffffffffull; }
 bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n,
                       uint32_t k) {
-  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return false;
+  if (!rec_k_ok(n_sessions, k)) return false;
   if (deny_n > (1ull << 32) || (!deny_bits && deny_n)) return false;
   return (ex_offsets == nullptr) == (ex_items == nullptr);
 }
@@ -177,152 +263,55 @@ int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint
                          : rec_run<false, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
 }
 
-// smatrix_cf_recommend_filtered_dev and smatrix_cf_recommend_sim_dev behind their refusals; sim: score by f_m, not by the cosine
-int rec_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
-                     const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k,
-                     uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream, bool sim, SimArgs f_m) {
+// every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
+// f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish
+template <bool R>
+int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream) {
   if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, f_m};
-  const int rc = rec_dispatch<false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, RecRank{});
-  rec_end(x, s);
-  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
-  rec_trim_all(x, false);
-  return rc;
+  RecCall c(self, hip_stream);
+  return c.finish(rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk));
 }
 
-// the host flavours of the same two
+// the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing)
 int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                       const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
                       uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m) {
   if (n_sessions == 0) return 0;
-  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
-  if (weights)
-    for (uint64_t i = 0; i < n_items; i++)
-      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = m->stream;
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
-  std::vector<uint64_t> rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
-  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
-  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
-  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
-  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
-  RecFilt f{};
-  f.m = f_m;
-  if (weights) {
-    x.h_w.need(std::max<uint64_t>(n_items, 1));
-    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
-    f.w = x.h_w.p;
-  }
-  if (ex_offsets) {
-    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
-    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
-    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
-  }
-  if (deny_n) {
-    x.h_deny.need(n_deny);
-    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
-    f.deny = x.h_deny.p; f.deny_n = deny_n;
-  }
-  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as smatrix_cf_recommend_batch's
-  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_dispatch<false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{});
-  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
-  rec_end(x, s);
-  HIP_OK(hipStreamSynchronize(s));
-  rec_trim_all(x, false);
-  return 0;
+  const uint64_t n = n_sessions;
+  if (!rec_host_weights_ok(weights, offsets, n)) return -1;
+  RecCall c(self);
+  RecScratch& x = c.x();
+  const RecList q = c.stage(n, offsets, items, x.h_off, x.h_items);
+  const RecFilt f = c.stage_filter(n, offsets, weights, ex_offsets, ex_items, deny_bits, deny_n, f_m);
+  x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
+  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, c.s));              // unused entries read 0, as cf_topk_batch's
+  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, c.s));
+  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{});
+  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, c.s));
+  return c.finish(0);
 }
 
-// smatrix_cf_rank_dev behind its refusals: rec_filtered_dev with the rank ending
-int rec_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
-                 const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, bool sim,
-                 SimArgs f_m, const RecRank& rk, uint32_t* d_n_candidates, void* hip_stream) {
-  if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const RecFilt f{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, f_m};
-  const int rc = rec_dispatch<true>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, 0u, nullptr, nullptr, d_n_candidates, f, sim, rk);
-  rec_end(x, s);
-  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
-  rec_trim_all(x, false);
-  return rc;
-}
-
-// the host flavour: rec_filtered_host's copies, and the target lists and the answers' [t_offsets[0], t_offsets[n]) beside them
+// the rank call's: the same staging, and the target lists and the answers' [t_offsets[0], t_offsets[n]) beside it
 int rec_rank_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                   const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, bool sim, SimArgs f_m,
                   const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores, uint32_t* n_candidates) {
   if (n_sessions == 0) return 0;
-  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0], n_t = t_offsets[n] - t_offsets[0];
-  if (weights)
-    for (uint64_t i = 0; i < n_items; i++)
-      if (!(weights[offsets[0] + i] >= 0.0) || !std::isfinite(weights[offsets[0] + i])) return -1;   // (before the device is touched)
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = m->stream;
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const uint64_t n_ex = ex_offsets ? ex_offsets[n] - ex_offsets[0] : 0, n_deny = (deny_n + 31) / 32;
-  std::vector<uint64_t> rel(n + 1), t_rel(n + 1), ex_rel(ex_offsets ? n + 1 : 0);
-  for (uint64_t i = 0; i <= n; i++) { rel[i] = offsets[i] - offsets[0]; t_rel[i] = t_offsets[i] - t_offsets[0]; }
-  for (uint64_t i = 0; i < ex_rel.size(); i++) ex_rel[i] = ex_offsets[i] - ex_offsets[0];
-  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_counts.need(n);
-  x.h_toff.need(n + 1); x.h_tg.need(std::max<uint64_t>(n_t, 1)); x.h_ranks.need(std::max<uint64_t>(n_t, 1)); x.h_scores.need(std::max<uint64_t>(n_t, 1));
-  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemcpyAsync(x.h_toff.p, t_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_t) HIP_OK(hipMemcpyAsync(x.h_tg.p, targets + t_offsets[0], n_t * 4, hipMemcpyHostToDevice, s));
-  RecFilt f{};
-  f.m = f_m;
-  if (weights) {
-    x.h_w.need(std::max<uint64_t>(n_items, 1));
-    if (n_items) HIP_OK(hipMemcpyAsync(x.h_w.p, weights + offsets[0], n_items * 8, hipMemcpyHostToDevice, s));
-    f.w = x.h_w.p;
-  }
-  if (ex_offsets) {
-    x.h_exoff.need(n + 1); x.h_ex.need(std::max<uint64_t>(n_ex, 1));
-    HIP_OK(hipMemcpyAsync(x.h_exoff.p, ex_rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (n_ex) HIP_OK(hipMemcpyAsync(x.h_ex.p, ex_items + ex_offsets[0], n_ex * 4, hipMemcpyHostToDevice, s));
-    f.ex_off = x.h_exoff.p; f.ex = x.h_ex.p;
-  }
-  if (deny_n) {
-    x.h_deny.need(n_deny);
-    HIP_OK(hipMemcpyAsync(x.h_deny.p, deny_bits, n_deny * 4, hipMemcpyHostToDevice, s));
-    f.deny = x.h_deny.p; f.deny_n = deny_n;
-  }
-  const RecRank rk{x.h_toff.p, x.h_tg.p, x.h_ranks.p, x.h_scores.p};
-  rec_dispatch<true>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, 0u, nullptr, nullptr, x.h_counts.p, f, sim, rk);
-  HIP_OK(hipMemcpyAsync(n_candidates, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
-  if (n_t) HIP_OK(hipMemcpyAsync(ranks + t_offsets[0], x.h_ranks.p, n_t * 4, hipMemcpyDeviceToHost, s));
-  if (n_t) HIP_OK(hipMemcpyAsync(scores + t_offsets[0], x.h_scores.p, n_t * 8, hipMemcpyDeviceToHost, s));
-  rec_end(x, s);
-  HIP_OK(hipStreamSynchronize(s));
-  rec_trim_all(x, false);
-  return 0;
+  const uint64_t n = n_sessions;
+  if (!rec_host_weights_ok(weights, offsets, n)) return -1;
+  RecCall c(self);
+  RecScratch& x = c.x();
+  const RecList q = c.stage(n, offsets, items, x.h_off, x.h_items), t = c.stage(n, t_offsets, targets, x.h_toff, x.h_tg);
+  const RecFilt f = c.stage_filter(n, offsets, weights, ex_offsets, ex_items, deny_bits, deny_n, f_m);
+  x.h_counts.need(n); x.h_ranks.need(std::max<uint64_t>(t.count, 1)); x.h_scores.need(std::max<uint64_t>(t.count, 1));
+  rec_dispatch<true>(c.m, x, c.s, (uint32_t)n, q.off, q.val, 0u, nullptr, nullptr, x.h_counts.p, f, sim,
+                     RecRank{t.off, t.val, x.h_ranks.p, x.h_scores.p});
+  HIP_OK(hipMemcpyAsync(n_candidates, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, c.s));
+  if (t.count) HIP_OK(hipMemcpyAsync(ranks + t_offsets[0], x.h_ranks.p, t.count * 4, hipMemcpyDeviceToHost, c.s));
+  if (t.count) HIP_OK(hipMemcpyAsync(scores + t_offsets[0], x.h_scores.p, t.count * 8, hipMemcpyDeviceToHost, c.s));
+  return c.finish(0);
 }
 
 // what both flavours of the rank call refuse before anything else (k: there is none)
@@ -346,49 +335,14 @@ extern "C" {
 
 int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, uint32_t k,
                                    uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream) {
-  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return -1;
-  if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  rec_run<false, false, false>(m, x, s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, RecFilt{}, RecRank{});
-  rec_end(x, s);
-  if (!hip_stream || rec_any_big(x)) HIP_OK(hipStreamSynchronize(s));   // (the kernels use the buffers rec_trim_all releases)
-  rec_trim_all(x, false);
-  return 0;
+  if (!rec_k_ok(n_sessions, k)) return -1;
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items, RecFilt{}, false, k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
 }
 
 int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, uint32_t k,
                                uint32_t* ids, double* scores, uint32_t* counts) {
-  if (k == 0 || k > 64 || n_sessions > 0xffffffffull) return -1;
-  if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = m->stream;
-  RecScratch& x = rec_of(m);
-  rec_begin(x, s);
-  const uint64_t n = n_sessions, n_items = offsets[n] - offsets[0];
-  std::vector<uint64_t> rel(n + 1);
-  for (uint64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
-  x.h_off.need(n + 1); x.h_items.need(std::max<uint64_t>(n_items, 1)); x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
-  HIP_OK(hipMemcpyAsync(x.h_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (n_items) HIP_OK(hipMemcpyAsync(x.h_items.p, items + offsets[0], n_items * 4, hipMemcpyHostToDevice, s));
-  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, s));                // unused entries read 0, as cf_topk_batch's
-  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, s));
-  rec_run<false, false, false>(m, x, s, (uint32_t)n, x.h_off.p, x.h_items.p, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, RecFilt{}, RecRank{});
-  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, s));
-  rec_end(x, s);
-  HIP_OK(hipStreamSynchronize(s));
-  rec_trim_all(x, false);
-  return 0;
+  if (!rec_k_ok(n_sessions, k)) return -1;
+  return rec_filtered_host(self, n_sessions, offsets, items, nullptr, nullptr, nullptr, nullptr, 0, k, ids, scores, counts, false, SimArgs{});
 }
 
 int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
@@ -396,8 +350,8 @@ int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const 
                                       const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids, double* d_scores,
                                       uint32_t* d_counts, void* hip_stream) {
   if (!rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  return rec_filtered_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k, d_ids,
-                          d_scores, d_counts, hip_stream, false, SimArgs{});
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items, RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{}}, false,
+                        k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
 }
 
 int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
@@ -414,8 +368,9 @@ int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint6
                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* d_ids,
                                  double* d_scores, uint32_t* d_counts, void* hip_stream) {
   if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  return rec_filtered_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k, d_ids,
-                          d_scores, d_counts, hip_stream, !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
+                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
+                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
 }
 
 int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
@@ -431,9 +386,10 @@ int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_of
                         double shrink, const uint64_t* d_t_offsets, const uint32_t* d_targets, uint32_t* d_ranks, double* d_scores,
                         uint32_t* d_n_candidates, void* hip_stream) {
   if (!rec_rank_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink, d_t_offsets, d_targets)) return -1;
-  return rec_rank_dev(self, n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n,
-                      !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, RecRank{d_t_offsets, d_targets, d_ranks, d_scores},
-                      d_n_candidates, hip_stream);
+  return rec_dev<true>(self, n_sessions, d_offsets, d_items,
+                       RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
+                       !sim_is_plain_cosine(sim, shrink), 0u, nullptr, nullptr, d_n_candidates,
+                       RecRank{d_t_offsets, d_targets, d_ranks, d_scores}, hip_stream);
 }
 
 int smatrix_cf_rank(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,

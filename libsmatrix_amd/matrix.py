@@ -148,11 +148,15 @@ def _check_k(k):
         raise ValueError("k must be 1..64, not %r" % (k,))
 
 
+def _weights_shape(weights, sessions):
+    if len(weights) != len(sessions) or any(len(w) != len(s) for w, s in zip(weights, sessions)):
+        raise ValueError("weights must hold one sequence per session, of the session's length")
+
+
 def _weights(weights, sessions):
     """per-session weight sequences shaped like sessions -> float64[total]; a shape that differs, a negative or a non-finite
     weight is a ValueError"""
-    if len(weights) != len(sessions) or any(len(w) != len(s) for w, s in zip(weights, sessions)):
-        raise ValueError("weights must hold one sequence per session, of the session's length")
+    _weights_shape(weights, sessions)
     flat = np.ascontiguousarray(np.concatenate([np.asarray(w, dtype=np.float64) for w in weights]) if len(weights)
                                 else np.zeros(0, np.float64))
     if not (np.isfinite(flat) & (flat >= 0)).all():
@@ -175,8 +179,11 @@ def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-def _p(a):
-    return a.ctypes.data_as(_lib.u32p)
+def _p(a, to=_lib.u32p):
+    return None if a is None else a.ctypes.data_as(to)
+
+
+_DP = C.POINTER(C.c_double)
 
 
 class SparseMatrix:
@@ -347,6 +354,25 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
 
+    def _cf_front(self, sessions, weights, exclude, deny, sim, shrink, targets=None):
+        """what cf_recommend_filtered, cf_rank and cf_explain do before their call: the arguments checked (every check before any
+        library call) and flattened.  -> (n, (sim's code, shrink), sess, filt, tgt, offsets, t_off): sess, filt and tgt are the C
+        arguments self .. weights, ex_offsets .. deny_n and t_offsets, targets (NULL for what was not given), offsets and t_off
+        the sessions' and the targets' offset arrays (t_off None without targets)"""
+        measure = _sim(sim), _shrink(shrink)
+        n = len(sessions)
+        w = None if weights is None else _weights(weights, sessions)
+        if targets is not None and len(targets) != n:
+            raise ValueError("targets must hold one id sequence per session")
+        if exclude is not None and len(exclude) != n:
+            raise ValueError("exclude must hold one id sequence per session")
+        offsets, items = _sessions(sessions)
+        t_off, tg = _sessions(targets) if targets is not None else (None, None)
+        ex_off, ex = _sessions(exclude) if exclude is not None else (None, None)
+        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        return (n, measure, (self._h, n, _p(offsets, _lib.u64p), _p(items), _p(w, _DP)), (_p(ex_off, _lib.u64p), _p(ex), _p(bits), deny_n),
+                (_p(t_off, _lib.u64p), _p(tg)), offsets, t_off)
+
     def cf_recommend_filtered(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_batch with "not these" and recency (include/smatrix_batch.h smatrix_cf_recommend_filtered), applied on
         the GPU before the k best are taken.  weights: per-session sequences shaped like sessions, finite and >= 0 (the term of
@@ -356,26 +382,15 @@ class SparseMatrix:
         sqrt(A) * sqrt(B) ("cosine"), A + B - cc ("jaccard") or A * B ("lift") over the totals A = self[a, 0], B = self[b, 0];
         shrink is a finite number >= 0.  The defaults make the call above"""
         _check_k(k)
-        code, h = _sim(sim), _shrink(shrink)
-        n = len(sessions)
-        w = None if weights is None else _weights(weights, sessions)
-        if exclude is not None and len(exclude) != n:
-            raise ValueError("exclude must hold one id sequence per session")
-        offsets, items = _sessions(sessions)
-        ex_off, ex = _sessions(exclude) if exclude is not None else (None, None)
-        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
         ids = np.zeros((n, k), dtype=np.uint32)
         scores = np.zeros((n, k), dtype=np.float64)
         counts = np.zeros(n, dtype=np.uint32)
-        dp = C.POINTER(C.c_double)
-        front = (self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
-                 None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
-                 None if bits is None else _p(bits), deny_n)
-        back = (k, ids.ctypes.data_as(_lib.u32p), scores.ctypes.data_as(dp), _p(counts))
-        if code == 0 and h == 0.0:
-            if n and self._lib.smatrix_cf_recommend_filtered(*front, *back) != 0:
+        back = (k, _p(ids), _p(scores, _DP), _p(counts))
+        if measure == (0, 0.0):
+            if n and self._lib.smatrix_cf_recommend_filtered(*sess, *filt, *back) != 0:
                 raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
-        elif n and self._lib.smatrix_cf_recommend_sim(*front, code, h, *back) != 0:
+        elif n and self._lib.smatrix_cf_recommend_sim(*sess, *filt, *measure, *back) != 0:
             raise ValueError("smatrix_cf_recommend_sim: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
         return ids, scores, counts
 
@@ -407,25 +422,11 @@ class SparseMatrix:
         a target is the number of the session's candidates that come before it (the position cf_recommend_filtered would give it,
         numbered on past 64) and its score the one returned there; RANK_NONE and 0.0 for a target that is no candidate (the id 0,
         an id in no scanned row, an item of the session, an excluded or denied id).  n_candidates is uncapped"""
-        code, h = _sim(sim), _shrink(shrink)
-        n = len(sessions)
-        w = None if weights is None else _weights(weights, sessions)
-        if len(targets) != n:
-            raise ValueError("targets must hold one id sequence per session")
-        if exclude is not None and len(exclude) != n:
-            raise ValueError("exclude must hold one id sequence per session")
-        offsets, items = _sessions(sessions)
-        t_off, tg = _sessions(targets)
-        ex_off, ex = _sessions(exclude) if exclude is not None else (None, None)
-        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
-        ranks = np.full(tg.size, RANK_NONE, dtype=np.uint32)
-        scores = np.zeros(tg.size, dtype=np.float64)
+        n, measure, sess, filt, tgt, _, t_off = self._cf_front(sessions, weights, exclude, deny, sim, shrink, targets)
+        ranks = np.full(int(t_off[-1]), RANK_NONE, dtype=np.uint32)
+        scores = np.zeros(ranks.size, dtype=np.float64)
         ncand = np.zeros(n, dtype=np.uint32)
-        dp = C.POINTER(C.c_double)
-        if n and self._lib.smatrix_cf_rank(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
-                                           None if ex_off is None else ex_off.ctypes.data_as(_lib.u64p), None if ex is None else _p(ex),
-                                           None if bits is None else _p(bits), deny_n, code, h, t_off.ctypes.data_as(_lib.u64p), _p(tg),
-                                           _p(ranks), scores.ctypes.data_as(dp), _p(ncand)) != 0:
+        if n and self._lib.smatrix_cf_rank(*sess, *filt, *measure, *tgt, _p(ranks), _p(scores, _DP), _p(ncand)) != 0:
             raise ValueError("smatrix_cf_rank: bad n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
         return ranks, scores, ncand
 
@@ -447,20 +448,12 @@ class SparseMatrix:
         self[a, t], or 0.0 and 0 when t is 0, a occurred earlier in the session, or a's row does not hold t.  Added left to right,
         a target's terms give the bytes of the score cf_recommend_filtered and cf_rank return for it; explain_table turns the
         arrays into sorted (item, cc, term) lists"""
-        code, h = _sim(sim), _shrink(shrink)
-        n = len(sessions)
-        w = None if weights is None else _weights(weights, sessions)
-        if len(targets) != n:
-            raise ValueError("targets must hold one id sequence per session")
-        offsets, items = _sessions(sessions)
-        t_off, tg = _sessions(targets)
+        n, measure, sess, _, tgt, offsets, t_off = self._cf_front(sessions, weights, None, None, sim, shrink, targets)
         e_off = np.zeros(n + 1, dtype=np.uint64)
         np.cumsum(np.diff(offsets) * np.diff(t_off), out=e_off[1:])
         terms = np.zeros(int(e_off[-1]), dtype=np.float64)
         cc = np.zeros(int(e_off[-1]), dtype=np.uint32)
-        dp = C.POINTER(C.c_double)
-        if n and self._lib.smatrix_cf_explain(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), None if w is None else w.ctypes.data_as(dp),
-                                              code, h, t_off.ctypes.data_as(_lib.u64p), _p(tg), terms.ctypes.data_as(dp), _p(cc)) != 0:
+        if n and self._lib.smatrix_cf_explain(*sess, *measure, *tgt, _p(terms, _DP), _p(cc)) != 0:
             raise ValueError("smatrix_cf_explain: bad n_sessions, weights, sim or shrink")
         return terms, cc, e_off
 
@@ -493,8 +486,8 @@ class SparseMatrix:
         co-occurrence with the rest of its session is in the very counts it is ranked by.  Evaluate with sessions that were not
         imported"""
         weights, exclude = measure.pop("weights", None), measure.pop("exclude", None)
-        if weights is not None and (len(weights) != len(sessions) or any(len(w) != len(s) for w, s in zip(weights, sessions))):
-            raise ValueError("weights must hold one sequence per session, of the session's length")
+        if weights is not None:
+            _weights_shape(weights, sessions)
         if exclude is not None and len(exclude) != len(sessions):
             raise ValueError("exclude must hold one id sequence per session")
         q, tg, qw, qe = [], [], [], []
