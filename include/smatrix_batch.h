@@ -281,6 +281,56 @@ int smatrix_cf_import_sessions(smatrix_t* self, size_t n_sessions, const uint64_
 int smatrix_cf_import_sessions_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
                                    const uint64_t* d_op_offsets, uint64_t total_ops, void* hip_stream);
 
+/* The write path with a window, amounts and a way back: what a session MEANS to the matrix is chosen by the caller, and a
+ * session that was imported can be taken out again.  Session s is the positions p = 0 .. L-1 of ids[offsets[s] .. offsets[s+1])
+ * (n_sessions + 1 non-decreasing offsets); its amounts are w_p = amounts[offsets[s] + p], or 1 everywhere with amounts NULL.
+ * The call applies, each exactly once:
+ *   head op    for every position p with w_p != 0:  op(id_p, 0, w_p).
+ *   pair op    for every ordered pair of positions (p, q), p != q, with w_p != 0 and w_q != 0:  op(id_p, id_q, min(w_p, w_q)),
+ *              provided that ALL of
+ *                window == 0 (no limit) or |p - q| <= window.  Distances are counted in positions; a position of amount 0 still
+ *                    occupies its place;
+ *                with SMATRIX_IMPORT_FORWARD, q > p: row a then holds what came AFTER a ("what came next").  Without the flag
+ *                    both directions are applied;
+ *                with SMATRIX_IMPORT_NO_SELF, id_p != id_q.  Without it an id that occurs twice counts against itself, as in
+ *                    smatrix_cf_import_sessions.
+ *   why min    the pair amount is min(w_p, w_q): it keeps the matrix symmetric without FORWARD, and with distinct ids it keeps
+ *              cc(a, b) <= min(total(a), total(b)), so the read path's guard cc > den -> 0 never fires on honest data.  A pair
+ *              amount of w_q alone would score a view-then-buy pair 0.
+ *   op         SMATRIX_OP_INCR or SMATRIX_OP_DECR.  A DECR of what an earlier INCR call with the same arguments applied restores
+ *              every value exactly (uint32, wrapping, as the reference's smatrix_decr); the cells and rows stay, as dead cells
+ *              (a pruning merge, min_value 1, removes them).  A DECR of what was never imported wraps.  A DECR call applies
+ *              all its pair ops first and its head ops after them, in internal batches of their own: a head cell that reaches
+ *              0 is the empty slot (quirk Q3) and cuts the probe chains of its row, so it has to be the LAST thing that happens
+ *              to a row that is forgotten altogether -- every cell of such a row then stays where it is, with the value 0.
+ *   id 0       is not special-cased, as in smatrix_cf_import_sessions.
+ * With (SMATRIX_OP_INCR, amounts NULL, window 0, flags 0) these are exactly the ops of smatrix_cf_import_sessions, and *n_ops is
+ *   the sum of L * L.  That call stays as it is; it is not routed through this one.
+ * Result: the batch contract at the top of this file for the whole call as if it were ONE batch: values are exact, row sizes and
+ *   `used` are the reference's.  The result does not depend on max_batch in anything the contract fixes.
+ * Bounded scratch: the ops are generated on the device and applied in internal batches of at most max_batch ops -- max_batch ==
+ *   0: 2^25; above 2^31: 2^31.  Device memory taken beyond the matrix is proportional to that bound plus 8 bytes per session
+ *   (and 8 per 2048 sessions), never to the number of ops.  The per-session op offsets the generator needs are made by the
+ *   library, on the device, with a scan over the sessions: _dev takes none and no total.  The generator walks a slot space of
+ *   L * min(L, 2 * window + 1) slots per session (FORWARD: L * min(L, window + 1); window 0: L * L) and compacts the slots that
+ *   are ops within each batch, so a batch may hold fewer than max_batch ops; one that holds none is not applied.
+ * *n_ops (a HOST pointer in both flavours, may be NULL) receives the number of ops applied.
+ * Returns -1 with nothing changed and *n_ops untouched for: an op other than INCR / DECR, unknown flag bits, n_sessions >= 2^32,
+ *   offsets that decrease, a slot space of 2^63 slots or more.  The host flavour finds the last two on the host, _dev on the
+ *   device before the first write (one 8-byte read-back).  0 otherwise, n_sessions == 0 included.
+ * Locks, mirror, files, streams are smatrix_cf_import_sessions_dev's: the matrix lock for the call; scalar writes still in the
+ *   host mirror are written back first and the mirror is dropped; column-0 adds are the single 64-bit add (no result array);
+ *   smatrix_stats_t::batches counts the internal batches, and a call during which SMATRIX_FLUSH_EVERY falls due takes ONE
+ *   checkpoint, at its end; file-backed matrices work unchanged.  The host flavour runs on the matrix's own stream and returns
+ *   when done.  _dev: arrays in device memory on the matrix's GPU, work on hip_stream, complete on it when the call returns
+ *   (NULL = the legacy default stream, synchronised before returning). */
+enum { SMATRIX_IMPORT_FORWARD = 1, SMATRIX_IMPORT_NO_SELF = 2 };   /* flags, may be or-ed */
+int smatrix_cf_import_events(smatrix_t* self, int op, size_t n_sessions, const uint64_t* offsets, const uint32_t* ids,
+                             const uint32_t* amounts, uint32_t window, uint32_t flags, uint64_t max_batch, uint64_t* n_ops);
+int smatrix_cf_import_events_dev(smatrix_t* self, int op, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
+                                 const uint32_t* d_amounts, uint32_t window, uint32_t flags, uint64_t max_batch,
+                                 uint64_t* n_ops, void* hip_stream);
+
 /* ---- whole-matrix export ------------------------------------------------- */
 enum { SMATRIX_EXPORT_TABLE = 0, SMATRIX_EXPORT_SORTED = 1 };
 

@@ -87,6 +87,8 @@ def load():
         "smatrix_cf_explain_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_int, C.c_double, V, V, V, C.c_uint64, V, V, V]),
         "smatrix_cf_import_sessions": (C.c_int, [H, C.c_size_t, u64p, u32p]),
         "smatrix_cf_import_sessions_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_uint64, V]),
+        "smatrix_cf_import_events": (C.c_int, [H, C.c_int, C.c_size_t, u64p, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint64, u64p]),
+        "smatrix_cf_import_events_dev": (C.c_int, [H, C.c_int, C.c_size_t, V, V, V, C.c_uint32, C.c_uint32, C.c_uint64, u64p, V]),
         "smatrix_export": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, u32p, u64p, u32p, u64p, u64p]),
         "smatrix_export_dev": (C.c_int, [H, C.c_int, C.c_uint64, C.c_uint64, V, V, V, u64p, u64p, V]),
         "smatrix_merge": (C.c_int, [H, H, C.c_int, C.c_uint64, u64p]),

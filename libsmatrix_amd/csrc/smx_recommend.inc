@@ -45,13 +45,15 @@ struct RecScratch {
   DevBuf<uint32_t> h_tg, h_ranks;
   DevBuf<uint64_t> h_eoff;                           // ... and the explain call's (smx_explain.inc): entry offsets (terms: h_scores, cc: h_ids),
   DevBuf<double> e_ra, e_cb;                         // and both its flavours' doubles per session entry and per target
+  DevBuf<uint32_t> h_amt, i_cnt;                     // ... and the event import's (smx_import.inc): amounts, the chunk's op counter,
+  DevBuf<uint64_t> i_soff, i_part;                   // the slots before every session and before every tile of sessions
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
   // EVERY buffer above, and the only list of them: the trim, the "any buffer big" test and the release are this visitor's
   template <typename Fn>
   void for_each_buf(Fn f) {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
-    f(h_eoff); f(e_ra); f(e_cb);
+    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part);
   }
 };
 

@@ -3428,5 +3428,8 @@ void smx_stream_release_device(smx_stream_t* st) {
 // ---- each session item's share of a candidate's score (smatrix_cf_explain) ------------------------
 #include "smx_explain.inc"
 
+// ---- windowed, weighted, reversible session import (smatrix_cf_import_events) ----------------------
+#include "smx_import.inc"
+
 // ---- the multi-GPU router (include/smatrix_shard.h) ---------------------------------------------------
 #include "smx_shard.inc"

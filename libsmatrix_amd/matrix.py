@@ -164,6 +164,35 @@ def _weights(weights, sessions):
     return flat
 
 
+IMPORT_FORWARD, IMPORT_NO_SELF = 1, 2                    # include/smatrix_batch.h SMATRIX_IMPORT_*
+
+
+def _amounts(amounts, sessions):
+    """cf_import_events' amounts -> uint32[total]: one entry per session, either a sequence of the session's length or one
+    integer for all its positions; integers in 0 .. 2**32 - 1.  Anything else is a ValueError"""
+    if isinstance(amounts, (str, bytes)) or not hasattr(amounts, "__len__") or len(amounts) != len(sessions):
+        raise ValueError("amounts must hold one entry per session: a sequence of the session's length, or one integer")
+    flat = []
+    for w, s in zip(amounts, sessions):
+        a = np.asarray(w)
+        if a.ndim == 0:
+            a = np.repeat(a, len(s))
+        if a.ndim != 1 or a.size != len(s):
+            raise ValueError("amounts must hold one entry per session: a sequence of the session's length, or one integer")
+        if a.size:
+            if a.dtype.kind not in "iu":
+                raise ValueError("amounts must be integers in 0 .. 2**32 - 1, not %r" % (a.dtype,))
+            wide = a.astype(np.int64 if a.dtype.kind == "i" else np.uint64)
+            if (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+                raise ValueError("amounts must be integers in 0 .. 2**32 - 1")
+        flat.append(a.astype(np.uint32))
+    return _u32(np.concatenate(flat) if flat else np.zeros(0, np.uint32))
+
+
+def _import_flags(forward, no_self):
+    return (IMPORT_FORWARD if forward else 0) | (IMPORT_NO_SELF if no_self else 0)
+
+
 def _deny_bitmap(deny):
     """a sequence of ids -> (bitmap uint32[(deny_n + 31) / 32], deny_n = the largest id + 1); (None, 0) for no id"""
     ids = np.unique(_u32(deny))
@@ -513,6 +542,39 @@ class SparseMatrix:
 
     def cf_import_sessions_dev(self, n_sessions, off_ptr, ids_ptr, op_off_ptr, total_ops, stream=None):
         self._lib.smatrix_cf_import_sessions_dev(self._h, n_sessions, off_ptr, ids_ptr, op_off_ptr, total_ops, stream)
+
+    def cf_import_events(self, sessions, amounts=None, window=0, forward=False, no_self=False, forget=False, max_batch=0):
+        """the write path with a window, amounts and a way back (include/smatrix_batch.h smatrix_cf_import_events): per position
+        p with amount w_p != 0 the head op (id_p, 0, w_p), per ordered pair of positions p != q with non-zero amounts the pair op
+        (id_p, id_q, min(w_p, w_q)) -- within `window` positions of each other (0: no limit), only q > p with forward, only
+        id_p != id_q with no_self.  amounts: one entry per session, a sequence of the session's length or one integer for all
+        its positions (None: 1 everywhere).  forget: the ops are decr, which takes an earlier import with the same arguments
+        out again, exactly.  Generated and applied on the GPU in internal batches of at most max_batch ops (0: 2**25).
+        -> the number of ops applied.  The defaults apply cf_import_sessions' ops"""
+        _check_u32("window", window)
+        if amounts is not None:
+            amounts = _amounts(amounts, sessions)
+        offsets, ids = _sessions(sessions)
+        n_ops = C.c_uint64(0)
+        if self._lib.smatrix_cf_import_events(self._h, OP_DECR if forget else OP_INCR, len(sessions), offsets.ctypes.data_as(_lib.u64p),
+                                              _p(ids), _p(amounts), int(window), _import_flags(forward, no_self), int(max_batch),
+                                              C.byref(n_ops)) != 0:
+            raise ValueError("smatrix_cf_import_events refused: more than 2**32 - 1 sessions, or 2**63 slots or more")
+        return n_ops.value
+
+    def cf_forget_sessions(self, sessions, **kw):
+        """cf_import_events(sessions, ..., forget=True): takes out what cf_import_events with the same arguments put in"""
+        return self.cf_import_events(sessions, **dict(kw, forget=True))
+
+    def cf_import_events_dev(self, op, n, off_ptr, ids_ptr, amounts_ptr, window, flags, max_batch=0, stream=None):
+        """the same on device arrays (raw pointers; amounts_ptr None: every amount 1; op OP_INCR or OP_DECR; flags IMPORT_FORWARD |
+        IMPORT_NO_SELF): -> the number of ops applied; the work is complete on `stream` when this returns"""
+        _check_u32("window", window)
+        n_ops = C.c_uint64(0)
+        if self._lib.smatrix_cf_import_events_dev(self._h, int(op), n, off_ptr, ids_ptr, amounts_ptr, int(window), int(flags), int(max_batch),
+                                                  C.byref(n_ops), stream) != 0:
+            raise ValueError("smatrix_cf_import_events_dev refused: op, flags, n, offsets that decrease, or 2**63 slots or more")
+        return n_ops.value
 
     # device-pointer flavours (raw pointers; stream = hipStream_t as int or None)
     def apply_batch_dev(self, op, n, x_ptr, y_ptr, v_ptr, out_ptr, stream=None):
