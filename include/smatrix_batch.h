@@ -271,6 +271,63 @@ int smatrix_cf_explain_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d
                            const uint32_t* d_targets, const uint64_t* d_e_offsets, uint64_t total,
                            double* d_terms, uint32_t* d_cc, void* hip_stream);
 
+/* The most popular items: the n ids with the largest totals (column 0), selected on the GPU over the whole directory -- what a
+ * short result is back-filled with (smatrix_cf_recommend_fill below), without an export of the matrix to the host.
+ *   candidates every id x != 0 for which smatrix_row_info(x) returns 1, with total(x) >= max(min_total, 1) and x not denied.
+ *              total(x) = what smatrix_get(x, 0) returns once the mirror is written back: a row without a head pair has total 0
+ *              and is no candidate, neither is an empty row (quirk Q3, set(x, 0, 0) on a new row) nor one whose head was
+ *              decremented to 0.  The deny bitmap is smatrix_cf_recommend_filtered's, bit for bit: ids >= deny_n are allowed,
+ *              deny_bits NULL goes with deny_n == 0.
+ *   order      by the key RkValue::make(x, total) of kernels/rank_key.hpp: total descending, equal totals by ascending id.  Keys
+ *              are unique, so the result depends on the matrix's contents alone, not on directory order, insertion history or growth.
+ *   output     the min(n, candidates) best, best first: ids[i] / totals[i], *n_found their number (a DEVICE pointer in _dev).  The
+ *              host flavour zero-fills the unused entries of ids and totals; _dev leaves them.
+ * Returns -1, outputs as they were and the device untouched, for n == 0, n > SMATRIX_POPULAR_MAX, deny_n > 2^32, deny_bits NULL
+ * with deny_n != 0, and ids, totals or n_found NULL.  0 otherwise, an empty matrix included (n_found = 0).
+ * How: a key per directory slot (one directory pass, one head-cell gather per row), a device-wide MSB radix select over the keys
+ * -- per pass a streaming 256-bin histogram and a one-wave pick, from the highest byte that is not 0 in every key down, so totals
+ * below 256 start at byte 4 of 8 --, the keys at or above the threshold collected with one atomic add per workgroup, and one
+ * workgroup that sorts them in LDS.  Everything between the first kernel and the stores is decided on the device: _dev makes no
+ * read-back at all.  Scratch: 8 bytes per directory slot, 8 n bytes and a control block of 8 KiB.
+ * Locks, the mirror, streams and scratch are the read path's (smatrix_cf_rank's): the matrix lock for the call, scalar writes still
+ * in the host mirror written back first, the scratch ordered behind the previous read-path call whatever its stream, hip_stream ==
+ * NULL synchronises; file-backed matrices work unchanged.  The matrix is not modified.  Deterministic. */
+#define SMATRIX_POPULAR_MAX 4096u
+int smatrix_cf_popular(smatrix_t* self, const uint32_t* deny_bits, uint64_t deny_n, uint32_t min_total,
+                       uint32_t n, uint32_t* ids, uint32_t* totals, uint32_t* n_found);
+int smatrix_cf_popular_dev(smatrix_t* self, const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t min_total,
+                           uint32_t n, uint32_t* d_ids, uint32_t* d_totals, uint32_t* d_n_found, void* hip_stream);
+
+/* k results for cold sessions: smatrix_cf_recommend_sim, then the free places of a short result filled from a list the caller
+ * gives -- popular (smatrix_cf_popular), trending or editorial; the library does not care which -- under the session's own filters.
+ * A new visitor, a session of long-tail items or one whose candidates are mostly excluded or denied still gets k results.
+ *   scored     exactly smatrix_cf_recommend_sim with the same arguments: n_scored[s] is its counts[s], and the entries
+ *              [s*k, s*k + n_scored[s]) of ids / scores are its bytes.  The same kernels are launched the same way; only what
+ *              follows them is new.
+ *   fill       when n_scored[s] < k, fill_ids[0 .. n_fill) is walked in list order and id f is appended with score +0.0 iff
+ *              f != 0, f is not an item of the session at any position (repeats and items of weight 0 included), f is not on
+ *              the session's exclusion list, f is not denied, and f is not in the session's result already, scored or filled
+ *              earlier -- which also settles repeats inside the list.  The walk stops at k entries or at the list's end;
+ *              counts[s] = n_scored[s] + the ids appended.  f needs no row in the matrix: the list is the caller's.  A filled id
+ *              is never one of the session's candidates: with n_scored[s] < k every candidate left is in the result already.
+ *   empty list fill_ids NULL with n_fill == 0: the call writes smatrix_cf_recommend_sim's bytes and n_scored = counts.
+ *   unused     entries beyond counts[s]: the host flavour zero-fills them, _dev leaves them.
+ * Cost beyond the sim call's: one launch, a wave per session.  A session with counts[s] == k ends after one load.  A session that
+ * fills tests 64 list ids a step, a lane each: about (L + E + k + 64) compares per id walked (L the session's length, E its
+ * exclusion list's), and at most k + L + E + (the zeros, denied ids and repeats in the list) ids are walked -- nothing for the short
+ * sessions that need filling.  _dev adds no read-back; the host flavour stages fill_ids once and copies n_scored back.
+ * Returns -1 for smatrix_cf_recommend_sim's refusals, word for word, and for n_scored NULL, fill_ids NULL with n_fill != 0 and
+ * n_fill >= 2^32 (before the device is touched, outputs as they were).  0 otherwise. */
+int smatrix_cf_recommend_fill(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                              const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                              const uint32_t* deny_bits, uint64_t deny_n, const uint32_t* fill_ids, uint64_t n_fill, int sim,
+                              double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts, uint32_t* n_scored);
+int smatrix_cf_recommend_fill_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                  const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                  const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_fill_ids, uint64_t n_fill,
+                                  int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
+                                  uint32_t* d_n_scored, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

@@ -24,6 +24,8 @@
 // smatrix_cf_rank (RecRank; k_rec_lds_rank<F>, k_rec_lds_rank_sim<F>, k_rec_gl_rank): the same tables with another ending.  Instead
 // of the k best slots, the session's targets are looked up in the finished table (they are never entered: tiers and table sizes
 // are the recommend call's) and the candidates that beat each are counted, rec_rank_table: one pass over the table per 64 targets.
+// smatrix_cf_recommend_fill (k_rec_fill, at the end of this file): the sim call's launches as they are, and one more behind them that
+// fills the free places of a short result from the caller's list under the session's own filters.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -654,5 +656,61 @@ __global__ __launch_bounds__(256) void k_rec_rank_fill(uint32_t n, RecRank rk) {
   for (uint64_t j = j0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < j1; j += (uint64_t)gridDim.x * blockDim.x) {
     rk.ranks[j] = 0xffffffffu;
     rk.scores[j] = 0.0;
+  }
+}
+
+// ---- smatrix_cf_recommend_fill: the free places of a short result, from the caller's list ---------------------------------
+// Enqueued behind the recommend launches of both tiers: it reads ids / counts as they wrote them and knows no tier.  A wave per
+// session: n_scored[s] = counts[s]; a full session ends there.  Otherwise the list is walked 64 ids a step, a lane each.  An id is
+// taken unless it is 0, denied, an item of the session or on its exclusion list (both 64 at a time through the wave), in the
+// result already -- the <= 64 ids of the result live in lanes, `mine`, 0 for a free place -- or the id of a lane below in the same
+// step.  Every test is a function of the id alone, so of the lanes of a step that hold one id the lowest decides for all.  The
+// lanes taken are numbered by mbcnt, cut at the room left, and handed to the lanes that own the new places: list order is kept.
+__global__ __launch_bounds__(256) void k_rec_fill(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
+                                                  const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids, double* scores,
+                                                  uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f) {
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t s = wave; s < n; s += nwaves) {                     // (wave-uniform throughout: the shuffles need every lane)
+    uint32_t have = counts[s];
+    if (lane == 0) n_scored[s] = have;
+    if (have >= k || n_fill == 0) continue;
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    const uint64_t e0 = f.ex_off ? f.ex_off[s] : 0ull, E = f.ex_off ? f.ex_off[s + 1] - e0 : 0ull;
+    uint32_t mine = lane < have ? ids[(uint64_t)s * k + lane] : 0u;
+    for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
+      const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
+      bool ok = fid != 0 && !rec_denied(f, fid);
+      if (!__any(ok)) continue;
+      for (uint64_t c0 = 0; c0 < L; c0 += 64) {
+        const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint64_t c0 = 0; c0 < E; c0 += 64) {
+        const uint32_t e = c0 + lane < E ? f.ex[e0 + c0 + lane] : 0u;
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);   // (every lane shuffles)
+        ok &= r != fid;                                             // in the result, scored or filled by an earlier step
+        ok &= !(j < lane && o == fid);                              // a lane below holds the same id
+      }
+      const uint64_t m = __ballot(ok);
+      if (m == 0) continue;
+      const uint32_t place = have + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const bool take = ok && place < k;                            // the room left is the cut
+      if (take) {
+        ids[(uint64_t)s * k + place] = fid;
+        scores[(uint64_t)s * k + place] = 0.0;
+      }
+      const uint32_t to = take ? place : 0xffffffffu;               // ... and the lane that owns the place holds the id from here on
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j);
+        if ((uint32_t)__shfl((int)to, (int)j) == lane) mine = o;
+      }
+      const uint32_t room = k - have, found = (uint32_t)__popcll(m);
+      have += found < room ? found : room;
+    }
+    if (lane == 0) counts[s] = have;
   }
 }

@@ -36,6 +36,7 @@ namespace smx {
 #include "kernels/sim.hpp"
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
+#include "kernels/popular.hpp"
 #include "kernels/explain.hpp"
 #include "kernels/import_events.hpp"
 #include "kernels/io_router.hpp"

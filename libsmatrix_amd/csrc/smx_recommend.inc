@@ -22,6 +22,8 @@
 // their _sim instances; with SMATRIX_SIM_COSINE and shrink 0 it IS the filtered call.
 // The rank call is the sim call with another ending (rec_run<.., .., true>): the answers are filled with "no answer", k_rec_lds_rank
 // stands for k_rec_lds, and k_rec_gl_rank for k_rec_gl_topk + k_rec_gl_merge; everything before the ending is shared.
+// The fill call (smatrix_cf_recommend_fill / _dev) is the sim call with ONE launch behind the driver's, rec_fill: k_rec_fill reads
+// the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).
 
 namespace {
 
@@ -47,13 +49,17 @@ struct RecScratch {
   DevBuf<double> e_ra, e_cb;                         // and both its flavours' doubles per session entry and per target
   DevBuf<uint32_t> h_amt, i_cnt;                     // ... and the event import's (smx_import.inc): amounts, the chunk's op counter,
   DevBuf<uint64_t> i_soff, i_part;                   // the slots before every session and before every tile of sessions
+  DevBuf<uint64_t> h_foff;                           // ... and the fill call's: the staged list (one list: two offsets), n_scored
+  DevBuf<uint32_t> h_fill, h_nsc;
+  DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
+  DevBuf<unsigned long long> p_keys, p_out;          // directory slot, the n keys collected (ids: h_ids, totals: h_counts, n: h_nsc)
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
   // EVERY buffer above, and the only list of them: the trim, the "any buffer big" test and the release are this visitor's
   template <typename Fn>
   void for_each_buf(Fn f) {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
-    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part);
+    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_foff); f(h_fill); f(h_nsc); f(p_ctl); f(p_keys); f(p_out);
   }
 };
 
@@ -253,6 +259,10 @@ bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_
   return (ex_offsets == nullptr) == (ex_items == nullptr);
 }
 bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
+// ... and the fill call on top of the sim call's
+bool rec_fill_args_ok(const void* fill_ids, uint64_t n_fill, const void* n_scored) {
+  return n_scored && n_fill < (1ull << 32) && (fill_ids || n_fill == 0);
+}
 // (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
 
 // the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending
@@ -265,20 +275,38 @@ int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint
                          : rec_run<false, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
 }
 
-// every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
-// f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish
-template <bool R>
-int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream) {
-  if (n_sessions == 0) return 0;
-  RecCall c(self, hip_stream);
-  return c.finish(rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk));
+// what smatrix_cf_recommend_fill adds to the sim call: the caller's list and where the scored counts go, all on the device
+struct RecFill {
+  const uint32_t* ids;
+  uint64_t n;
+  uint32_t* n_scored;
+};
+// behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session
+void rec_fill(hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k, const RecFill& fl, uint32_t* d_ids,
+              double* d_scores, uint32_t* d_counts, const RecFilt& f) {
+  hipLaunchKernelGGL(k_rec_fill, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, n, d_off, d_items, k, fl.ids,
+                     (uint32_t)fl.n, d_ids, d_scores, d_counts, fl.n_scored, f);
+  HIP_OK(hipGetLastError());
 }
 
-// the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing)
+// every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
+// f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish.  fl: the fill call, its kernel behind
+// the driver's
+template <bool R>
+int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream, const RecFill* fl = nullptr) {
+  if (n_sessions == 0) return 0;
+  RecCall c(self, hip_stream);
+  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk);
+  if (fl && rc == 0) rec_fill(c.s, (uint32_t)n_sessions, d_offsets, d_items, k, *fl, d_ids, d_scores, d_counts, f);
+  return c.finish(rc);
+}
+
+// the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing);
+// fl: the fill call, with the HOST's list and n_scored -- the list goes through the stager as a list of lists that holds one list
 int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                       const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
-                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m) {
+                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m, const RecFill* fl = nullptr) {
   if (n_sessions == 0) return 0;
   const uint64_t n = n_sessions;
   if (!rec_host_weights_ok(weights, offsets, n)) return -1;
@@ -290,6 +318,13 @@ int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offset
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, c.s));              // unused entries read 0, as cf_topk_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, c.s));
   rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{});
+  if (fl) {
+    const uint64_t one_list[2] = {0, fl->n};
+    const RecList l = c.stage(1, one_list, fl->ids, x.h_foff, x.h_fill);
+    x.h_nsc.need(n);
+    rec_fill(c.s, (uint32_t)n, q.off, q.val, k, RecFill{l.val, l.count, x.h_nsc.p}, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
+    HIP_OK(hipMemcpyAsync(fl->n_scored, x.h_nsc.p, n * 4, hipMemcpyDeviceToHost, c.s));
+  }
   HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, c.s));
   HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, c.s));
   HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, c.s));
@@ -381,6 +416,30 @@ int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t*
   if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
   return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
                            !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
+}
+
+int smatrix_cf_recommend_fill_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                  const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                  const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_fill_ids, uint64_t n_fill, int sim,
+                                  double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts, uint32_t* d_n_scored,
+                                  void* hip_stream) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
+  if (!rec_fill_args_ok(d_fill_ids, n_fill, d_n_scored)) return -1;
+  const RecFill fl{d_fill_ids, n_fill, d_n_scored};
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
+                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
+                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, &fl);
+}
+
+int smatrix_cf_recommend_fill(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                              const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n,
+                              const uint32_t* fill_ids, uint64_t n_fill, int sim, double shrink, uint32_t k, uint32_t* ids, double* scores,
+                              uint32_t* counts, uint32_t* n_scored) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
+  if (!rec_fill_args_ok(fill_ids, n_fill, n_scored)) return -1;
+  const RecFill fl{fill_ids, n_fill, n_scored};
+  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
+                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, &fl);
 }
 
 int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,

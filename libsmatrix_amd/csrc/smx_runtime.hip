@@ -3431,5 +3431,8 @@ void smx_stream_release_device(smx_stream_t* st) {
 // ---- windowed, weighted, reversible session import (smatrix_cf_import_events) ----------------------
 #include "smx_import.inc"
 
+// ---- the most popular items, for filling short results (smatrix_cf_popular) -------------------------
+#include "smx_popular.inc"
+
 // ---- the multi-GPU router (include/smatrix_shard.h) ---------------------------------------------------
 #include "smx_shard.inc"

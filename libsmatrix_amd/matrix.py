@@ -193,6 +193,34 @@ def _import_flags(forward, no_self):
     return (IMPORT_FORWARD if forward else 0) | (IMPORT_NO_SELF if no_self else 0)
 
 
+POPULAR_MAX = 4096                                       # include/smatrix_batch.h SMATRIX_POPULAR_MAX
+
+
+def _popular_args(n, min_total):
+    """cf_popular's n / min_total: n an integer in 1 .. POPULAR_MAX, min_total a uint32; anything else is a ValueError"""
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or not 1 <= n <= POPULAR_MAX:
+        raise ValueError("n must be an integer in 1 .. %d, not %r" % (POPULAR_MAX, n))
+    _check_u32("min_total", min_total)
+
+
+def _fill_ids(fill):
+    """cf_recommend_filled's list -> uint32[n_fill]: a flat sequence of integers in 0 .. 2**32 - 1, which may be empty.  Anything
+    else is a ValueError"""
+    if fill is None or isinstance(fill, (str, bytes)) or not hasattr(fill, "__len__"):
+        raise ValueError("fill must be a sequence of ids, not %r" % (fill,))
+    a = np.asarray(fill)
+    if a.ndim != 1 or a.size > 0xFFFFFFFF:
+        raise ValueError("fill must be a flat sequence of fewer than 2**32 ids")
+    if a.size == 0:
+        return np.zeros(0, np.uint32)
+    if a.dtype.kind not in "iu":
+        raise ValueError("fill must hold integers in 0 .. 2**32 - 1, not %r" % (a.dtype,))
+    wide = a.astype(np.int64 if a.dtype.kind == "i" else np.uint64)
+    if (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+        raise ValueError("fill must hold integers in 0 .. 2**32 - 1")
+    return _u32(a)
+
+
 def _deny_bitmap(deny):
     """a sequence of ids -> (bitmap uint32[(deny_n + 31) / 32], deny_n = the largest id + 1); (None, 0) for no id"""
     ids = np.unique(_u32(deny))
@@ -443,6 +471,57 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_sim_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
                                                   deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_sim_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
+
+    def cf_popular(self, n, deny=None, min_total=1):
+        """the most popular items (include/smatrix_batch.h smatrix_cf_popular): the up to n <= POPULAR_MAX ids x != 0 with the
+        largest totals self[x, 0] >= max(min_total, 1), the ids of `deny` left out, selected on the GPU over the whole matrix.
+        -> (ids uint32[n_found], totals uint32[n_found]), total descending, equal totals by ascending id"""
+        _popular_args(n, min_total)
+        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        ids = np.zeros(int(n), dtype=np.uint32)
+        totals = np.zeros(int(n), dtype=np.uint32)
+        found = C.c_uint32(0)
+        if self._lib.smatrix_cf_popular(self._h, _p(bits), deny_n, int(min_total), int(n), _p(ids), _p(totals), C.byref(found)) != 0:
+            raise ValueError("smatrix_cf_popular: bad n or deny bitmap")
+        return ids[:found.value].copy(), totals[:found.value].copy()
+
+    def cf_popular_dev(self, n, deny_ptr, deny_n, min_total, ids_ptr, totals_ptr, n_found_ptr, stream=None):
+        """the same on device arrays (raw pointers; deny_ptr None with deny_n 0 for no bitmap): deny uint32[(deny_n + 31) / 32],
+        ids uint32[n], totals uint32[n], n_found uint32[1].  No read-back: nothing is returned, the entries beyond n_found are
+        left as they were"""
+        _popular_args(n, min_total)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_popular_dev(self._h, deny_ptr, deny_n, int(min_total), int(n), ids_ptr, totals_ptr, n_found_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_popular_dev: bad n, deny bitmap or outputs")
+
+    def cf_recommend_filled(self, sessions, k, fill, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_filtered, then the free places of a short result filled from `fill` (include/smatrix_batch.h
+        smatrix_cf_recommend_fill): a sequence of ids -- cf_popular's, trending, editorial --, walked in order; an id is appended
+        with score 0.0 unless it is 0, an item of the session, excluded, denied or in the result already.
+        -> (ids[n,k], scores[n,k] float64, counts[n], n_scored[n]): the first n_scored[s] entries of session s are
+        cf_recommend_filtered's, the entries up to counts[s] are filled"""
+        _check_k(k)
+        fill = _fill_ids(fill)
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        ids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        n_scored = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_fill(*sess, *filt, _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids),
+                                                     _p(scores, _DP), _p(counts), _p(n_scored)) != 0:
+            raise ValueError("smatrix_cf_recommend_fill: bad k, n_sessions, weights, exclusion lists, deny bitmap, fill, sim or shrink")
+        return ids, scores, counts, n_scored
+
+    def cf_recommend_fill_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, fill_ptr, n_fill, sim,
+                              shrink, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given): cf_recommend_sim_dev's, and fill uint32[n_fill]
+        (None with n_fill 0: no list), n_scored uint32[n]"""
+        _check_k(k)
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
+                                                   fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, fill, sim or shrink")
 
     def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """where given items land in each session's ranking (include/smatrix_batch.h smatrix_cf_rank): cf_recommend_filtered's
