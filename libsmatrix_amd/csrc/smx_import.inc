@@ -1,7 +1,8 @@
-// smx_import.inc -- the windowed, weighted, reversible session import (include/smatrix_batch.h smatrix_cf_import_events / _dev),
-// host side.  Included by smx_runtime.hip inside the translation unit, after smx_explain.inc (uses smx_recommend.inc's call scope
-// RecCall with its stager and its RecScratch, and the write path's apply_dev_locked, CkptAfter and cache_sync); the device code is
-// kernels/import_events.hpp.
+// smx_import.inc -- the session imports, host side: the windowed, weighted, reversible one (include/smatrix_batch.h
+// smatrix_cf_import_events / _dev) and the reference example's loop (smatrix_cf_import_sessions / _dev).  Included by smx_runtime.hip
+// inside the translation unit, after smx_explain.inc (uses smx_recommend.inc's call scope RecCall with its stager and its
+// RecScratch, and the write path's apply_dev_locked, CkptAfter and cache_sync); the device code is kernels/import_events.hpp and,
+// for the old call, k_cf_expand of kernels/rows.hpp.
 //
 // Inside a RecCall (the matrix lock, the stream, behind the previous call on the scratch; its finish applies the synchronisation
 // rule and the trim), with a CkptAfter declared in front of it, imp_run:
@@ -19,11 +20,14 @@
 // that holds x is forgotten, and then every pair cell of the row is forgotten too: with the head ops last the row ends with all
 // its cells at 0 and in place, in every order the two groups of batches run in.  INCR is one pass.
 // The host flavour checks the offsets and the total before it touches the device, then stages offsets, ids and amounts with the
-// scope's stager.  The old call, smatrix_cf_import_sessions, is not routed through any of this.
+// scope's stager.
+// The old call, smatrix_cf_import_sessions, shares the host side and not the generator: its host flavour is the same scope, CkptAfter
+// and stager (and one buffer more, the op offsets the host worked out), but its ops come from ses_run -- k_cf_expand over those op
+// offsets, L * L ops a session, no scan, no compaction, no read-back.  Its _dev flavour has no scratch and opens no scope.
 
 namespace {
 
-constexpr uint64_t IMP_DEFAULT_BATCH = 1ull << 25;     // CF_IMPORT_CHUNK
+constexpr uint64_t IMP_DEFAULT_BATCH = 1ull << 25;     // (= CF_IMPORT_CHUNK, the old call's)
 constexpr uint64_t IMP_MAX_BATCH = 1ull << 31;         // (a write batch holds fewer than 2^32 ops)
 static_assert(IMP_FORWARD == SMATRIX_IMPORT_FORWARD && IMP_NO_SELF == SMATRIX_IMPORT_NO_SELF, "kernels/import_events.hpp");
 
@@ -83,9 +87,68 @@ int imp_run(smatrix_t* self, RecCall& c, int op, uint32_t n, const uint64_t* d_o
   return 0;
 }
 
+// the old call on stream s, under the matrix lock with the mirror dropped: the L * L incr ops of every session (d_op_offsets[s] = the
+// ops before session s, the last entry = total_ops) generated in chunks of CF_IMPORT_CHUNK ops and applied as ordinary incr batches
+constexpr uint64_t CF_IMPORT_CHUNK = 1ull << 25;
+void ses_run(smatrix_t* self, Matrix* m, hipStream_t s, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
+             const uint64_t* d_op_offsets, uint64_t total_ops) {
+  const size_t chunk = (size_t)std::min<uint64_t>(total_ops, CF_IMPORT_CHUNK);
+  m->sx.need(chunk); m->sy.need(chunk); m->sv.need(chunk); m->so.need(chunk);
+  for (uint64_t t0 = 0; t0 < total_ops; t0 += CF_IMPORT_CHUNK) {
+    const uint32_t n = (uint32_t)std::min<uint64_t>(CF_IMPORT_CHUNK, total_ops - t0);
+    hipLaunchKernelGGL(k_cf_expand, dim3(blocks_for(n)), dim3(256), 0, s, t0, n, (uint32_t)n_sessions, d_offsets, d_ids,
+                       d_op_offsets, m->sx.p, m->sy.p, m->sv.p);
+    HIP_OK(hipGetLastError());
+    m->no_ret = true;
+    apply_dev_locked(self, OP_INCR, n, m->sx.p, m->sy.p, m->sv.p, m->so.p, s);
+    m->no_ret = false;
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- CF-recommender write path (examples/cf_recommender.c:36-47) ------------------------------------------------
+int smatrix_cf_import_sessions_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
+                                   const uint64_t* d_op_offsets, uint64_t total_ops, void* hip_stream) {
+  if (n_sessions == 0 || total_ops == 0) return 0;
+  if (n_sessions > 0xffffffffull) return -1;
+  Matrix* m = M(self);
+  set_device(m);
+  CkptAfter ckpt(self);                                  // (a checkpoint that falls due is taken after m->mu is released)
+  std::lock_guard<std::mutex> g(m->mu);
+  cache_sync(m, true);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
+  ses_run(self, m, s, n_sessions, d_offsets, d_ids, d_op_offsets, total_ops);
+  if (!hip_stream) HIP_OK(hipStreamSynchronize(s));
+  return 0;
+}
+
+int smatrix_cf_import_sessions(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* ids) {
+  if (n_sessions == 0) return 0;
+  std::vector<uint64_t> op_off(n_sessions + 1, 0);
+  for (size_t i = 0; i < n_sessions; i++) {
+    if (offsets[i + 1] < offsets[i]) return -1;
+    const uint64_t L = offsets[i + 1] - offsets[i];
+    op_off[i + 1] = op_off[i] + L * L;
+  }
+  const uint64_t total = op_off[n_sessions];
+  if (total == 0) return 0;
+  if (n_sessions > 0xffffffffull) return -1;
+  CkptAfter ckpt(self);
+  RecCall c(self);
+  RecScratch& x = c.x();
+  const RecList q = c.stage(n_sessions, offsets, ids, x.h_off, x.h_items);
+  c.rel.push_back(std::move(op_off));                     // (read by the copy in flight: alive until finish)
+  x.h_opoff.need(n_sessions + 1);
+  HIP_OK(hipMemcpyAsync(x.h_opoff.p, c.rel.back().data(), (n_sessions + 1) * 8, hipMemcpyHostToDevice, c.s));
+  cache_sync(c.m, true);
+  ses_run(self, c.m, c.s, n_sessions, q.off, q.val, x.h_opoff.p, total);
+  return c.finish(0);
+}
+
+// ---- the same with a window, amounts and a way back ---------------------------------------------------------------
 
 int smatrix_cf_import_events_dev(smatrix_t* self, int op, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
                                  const uint32_t* d_amounts, uint32_t window, uint32_t flags, uint64_t max_batch,

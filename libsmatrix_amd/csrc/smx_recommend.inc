@@ -5,7 +5,8 @@
 //
 // Three layers, top down:
 //   the extern "C" symbols   refuse bad arguments, then name what the call was given: a RecFilt, a measure, a RecRank
-//   RecCall                  ONE scope for every call on the read path's scratch (smx_explain.inc's two as well): the matrix lock,
+//   RecCall                  ONE scope for every call on the read path's scratch (the files included behind this one as well: the
+//                            item-neighbour calls' host flavours, the explain call, both imports, the popular call): the matrix lock,
 //                            the scalar mirror written back (cache_sync), the stream, the wait for the call before, and at finish
 //                            the event, the synchronisation rule and the trim.  Its stagers carry a host flavour's arrays to the
 //                            device: stage (a window of a list of lists: sessions, exclusion lists, targets), stage_weights,
@@ -49,6 +50,7 @@ struct RecScratch {
   DevBuf<double> e_ra, e_cb;                         // and both its flavours' doubles per session entry and per target
   DevBuf<uint32_t> h_amt, i_cnt;                     // ... and the event import's (smx_import.inc): amounts, the chunk's op counter,
   DevBuf<uint64_t> i_soff, i_part;                   // the slots before every session and before every tile of sessions
+  DevBuf<uint64_t> h_opoff;                          // ... and the old import's: the ops before every session
   DevBuf<uint64_t> h_foff;                           // ... and the fill call's: the staged list (one list: two offsets), n_scored
   DevBuf<uint32_t> h_fill, h_nsc;
   DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
@@ -59,7 +61,7 @@ struct RecScratch {
   void for_each_buf(Fn f) {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
-    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_foff); f(h_fill); f(h_nsc); f(p_ctl); f(p_keys); f(p_out);
+    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(p_ctl); f(p_keys); f(p_out);
   }
 };
 

@@ -740,7 +740,7 @@ struct Matrix {
   static constexpr bool cold_far = true;    // the walks of a clustered table's cold rounds go through the far join (a wave per key: 37 vs 69 ms)
   DevBuf<unsigned long long> cold_keys[3];   // the distinct pending keys, packed; what a round leaves deferred
   void* ex = nullptr;                   // ExportScratch (smx_export.inc): smatrix_export's pooled scratch
-  void* rec = nullptr;                  // RecScratch (smx_recommend.inc): smatrix_cf_recommend_batch's pooled scratch
+  void* rec = nullptr;                  // RecScratch (smx_recommend.inc): the pooled scratch of every call on the read path's scope (RecCall)
   void* mg = nullptr;                   // MergeScratch (smx_merge.inc): smatrix_merge / smatrix_import_csr's record buffers, helper stream and events
 };
 
@@ -2857,52 +2857,6 @@ int smatrix_getrow_batch(smatrix_t* self, size_t n, const uint32_t* x, const uin
   return 0;
 }
 
-// ---- CF-recommender read path (include/smatrix_batch.h) ------------------------------------------
-int smatrix_cf_neighbors_batch_dev(smatrix_t* self, size_t n, const uint32_t* d_items,
-                                   const uint64_t* d_offsets, uint32_t* d_ids, double* d_scores,
-                                   uint32_t* d_counts, void* hip_stream) {
-  if (n == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  uint32_t grid = std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384);
-  hipLaunchKernelGGL(k_cf_neighbors, dim3(grid), dim3(256), 0, s, m->d_dir, m->dir_size - 1, m->arena.base,
-                     (uint32_t)n, d_items, d_offsets, d_ids, d_scores, d_counts);
-  HIP_OK(hipGetLastError());
-  if (!hip_stream) HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int smatrix_cf_neighbors_batch(smatrix_t* self, size_t n, const uint32_t* items, const uint64_t* offsets,
-                               uint32_t* ids, double* scores, uint32_t* counts) {
-  if (n == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  const uint64_t total = offsets[n];
-  uint32_t *d_items = nullptr, *d_ids = nullptr, *d_counts = nullptr;
-  uint64_t* d_off = nullptr;
-  double* d_scores = nullptr;
-  dev_malloc(&d_items, n * 4);
-  dev_malloc(&d_off, (n + 1) * 8);
-  dev_malloc(&d_counts, n * 4);
-  dev_malloc(&d_ids, std::max<uint64_t>(total, 1) * 4);
-  dev_malloc(&d_scores, std::max<uint64_t>(total, 1) * 8);
-  HIP_OK(hipMemset(d_ids, 0, std::max<uint64_t>(total, 1) * 4));        // slots beyond a row's count read 0
-  HIP_OK(hipMemset(d_scores, 0, std::max<uint64_t>(total, 1) * 8));
-  HIP_OK(hipMemcpy(d_items, items, n * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice));
-  smatrix_cf_neighbors_batch_dev(self, n, d_items, d_off, d_ids, d_scores, d_counts, nullptr);
-  HIP_OK(hipMemcpy(counts, d_counts, n * 4, hipMemcpyDeviceToHost));
-  if (total) {
-    HIP_OK(hipMemcpy(ids, d_ids, total * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(scores, d_scores, total * 8, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(d_items); (void)hipFree(d_off); (void)hipFree(d_counts); (void)hipFree(d_ids); (void)hipFree(d_scores);
-  return 0;
-}
-
 static void row_info_locked(Matrix* m, uint32_t x, uint32_t* four);
 
 // ---- the reference's scalar entry points ----------------------------------------------------------
@@ -3089,104 +3043,6 @@ uint32_t smatrix_getrow(smatrix_t* self, uint32_t x, uint32_t* ret, size_t ret_l
   if (count) HIP_OK(hipMemcpy(ret, m->row_ret.p, (size_t)count * 8, hipMemcpyDeviceToHost));
   if (m->row_ret.cap > ((size_t)64 << 20)) m->row_ret.release();
   return count;
-}
-
-// the k best neighbours per item (k <= 64); ids / scores hold n * k entries, item i's at [i*k, i*k + counts[i])
-int smatrix_cf_topk_batch_dev(smatrix_t* self, size_t n, const uint32_t* d_items, uint32_t k, uint32_t* d_ids,
-                              double* d_scores, uint32_t* d_counts, void* hip_stream) {
-  if (k == 0 || k > 64) return -1;
-  if (n == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, false);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  uint32_t grid = std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384);
-  hipLaunchKernelGGL(k_cf_topk, dim3(grid), dim3(256), 0, s, m->d_dir, m->dir_size - 1, m->arena.base, (uint32_t)n, d_items, k,
-                     d_ids, d_scores, d_counts);
-  HIP_OK(hipGetLastError());
-  if (!hip_stream) HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int smatrix_cf_topk_batch(smatrix_t* self, size_t n, const uint32_t* items, uint32_t k, uint32_t* ids, double* scores,
-                          uint32_t* counts) {
-  if (k == 0 || k > 64) return -1;
-  if (n == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  uint32_t *d_items = nullptr, *d_ids = nullptr, *d_counts = nullptr;
-  double* d_scores = nullptr;
-  dev_malloc(&d_items, n * 4);
-  dev_malloc(&d_counts, n * 4);
-  dev_malloc(&d_ids, n * k * 4);
-  dev_malloc(&d_scores, n * k * 8);
-  HIP_OK(hipMemset(d_ids, 0, n * k * 4));
-  HIP_OK(hipMemset(d_scores, 0, n * k * 8));
-  HIP_OK(hipMemcpy(d_items, items, n * 4, hipMemcpyHostToDevice));
-  smatrix_cf_topk_batch_dev(self, n, d_items, k, d_ids, d_scores, d_counts, nullptr);
-  HIP_OK(hipMemcpy(counts, d_counts, n * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(ids, d_ids, n * k * 4, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(scores, d_scores, n * k * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(d_items); (void)hipFree(d_counts); (void)hipFree(d_ids); (void)hipFree(d_scores);
-  return 0;
-}
-
-// ---- CF-recommender write path (examples/cf_recommender.c:36-47) ------------------------------------------------
-// n_sessions sessions, session s = ids[offsets[s] .. offsets[s+1]); d_op_offsets[s] = sum of L*L over the sessions before s
-// (n_sessions + 1 entries, the last one = total_ops).  The L*L incr ops of every session are generated on the device in
-// chunks of CF_IMPORT_CHUNK ops and applied as ordinary incr batches.
-static constexpr uint64_t CF_IMPORT_CHUNK = 1ull << 25;
-int smatrix_cf_import_sessions_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_ids,
-                                   const uint64_t* d_op_offsets, uint64_t total_ops, void* hip_stream) {
-  if (n_sessions == 0 || total_ops == 0) return 0;
-  if (n_sessions > 0xffffffffull) return -1;
-  Matrix* m = M(self);
-  set_device(m);
-  CkptAfter ckpt(self);                                  // (a checkpoint that falls due is taken after m->mu is released)
-  std::lock_guard<std::mutex> g(m->mu);
-  cache_sync(m, true);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);   // NULL = the legacy default stream
-  const size_t chunk = (size_t)std::min<uint64_t>(total_ops, CF_IMPORT_CHUNK);
-  m->sx.need(chunk); m->sy.need(chunk); m->sv.need(chunk); m->so.need(chunk);
-  for (uint64_t t0 = 0; t0 < total_ops; t0 += CF_IMPORT_CHUNK) {
-    const uint32_t n = (uint32_t)std::min<uint64_t>(CF_IMPORT_CHUNK, total_ops - t0);
-    hipLaunchKernelGGL(k_cf_expand, dim3(blocks_for(n)), dim3(256), 0, s, t0, n, (uint32_t)n_sessions, d_offsets, d_ids,
-                       d_op_offsets, m->sx.p, m->sy.p, m->sv.p);
-    HIP_OK(hipGetLastError());
-    m->no_ret = true;
-    apply_dev_locked(self, OP_INCR, n, m->sx.p, m->sy.p, m->sv.p, m->so.p, s);
-    m->no_ret = false;
-  }
-  if (!hip_stream) HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int smatrix_cf_import_sessions(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* ids) {
-  if (n_sessions == 0) return 0;
-  Matrix* m = M(self);
-  set_device(m);
-  std::vector<uint64_t> op_off(n_sessions + 1, 0);
-  for (size_t i = 0; i < n_sessions; i++) {
-    if (offsets[i + 1] < offsets[i]) return -1;
-    const uint64_t L = offsets[i + 1] - offsets[i];
-    op_off[i + 1] = op_off[i] + L * L;
-  }
-  const uint64_t n_ids = offsets[n_sessions] - offsets[0], total = op_off[n_sessions];
-  if (total == 0) return 0;
-  uint64_t *d_off = nullptr, *d_op = nullptr;
-  uint32_t* d_ids = nullptr;
-  dev_malloc(&d_off, (n_sessions + 1) * 8);
-  dev_malloc(&d_op, (n_sessions + 1) * 8);
-  dev_malloc(&d_ids, std::max<uint64_t>(n_ids, 1) * 4);
-  std::vector<uint64_t> rel(n_sessions + 1);
-  for (size_t i = 0; i <= n_sessions; i++) rel[i] = offsets[i] - offsets[0];
-  HIP_OK(hipMemcpy(d_off, rel.data(), (n_sessions + 1) * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_op, op_off.data(), (n_sessions + 1) * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(d_ids, ids + offsets[0], n_ids * 4, hipMemcpyHostToDevice));
-  const int rc = smatrix_cf_import_sessions_dev(self, n_sessions, d_off, d_ids, d_op, total, nullptr);
-  (void)hipFree(d_off); (void)hipFree(d_op); (void)hipFree(d_ids);
-  return rc;
 }
 
 // Capacity hint (like vector::reserve): map at least `bytes` of row arena now, so that growth steps -- calls into the
@@ -3422,13 +3278,16 @@ void smx_stream_release_device(smx_stream_t* st) {
 // ---- merge of two matrices, CSR import (smatrix_merge / smatrix_import_csr) ------
 #include "smx_merge.inc"
 
-// ---- session recommendations (include/smatrix_batch.h) ------------------------------------------
+// ---- session recommendations (include/smatrix_batch.h), and the read path's call scope RecCall -----
 #include "smx_recommend.inc"
+
+// ---- an item's neighbours, all or the k best (smatrix_cf_neighbors_batch, smatrix_cf_topk_batch) ----
+#include "smx_neighbors.inc"
 
 // ---- each session item's share of a candidate's score (smatrix_cf_explain) ------------------------
 #include "smx_explain.inc"
 
-// ---- windowed, weighted, reversible session import (smatrix_cf_import_events) ----------------------
+// ---- the session imports (smatrix_cf_import_sessions, smatrix_cf_import_events) ----------------------
 #include "smx_import.inc"
 
 // ---- the most popular items, for filling short results (smatrix_cf_popular) -------------------------
