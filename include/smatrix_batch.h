@@ -190,6 +190,45 @@ int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint6
                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k,
                                  uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
 
+/* Diverse results: smatrix_cf_recommend_sim with at most `cap` results of a session from one group -- brand, category, seller; the
+ * library does not care which.  The rule runs on the GPU over the session's WHOLE ranking, before the cut at k: a session whose best
+ * 64 candidates come from three brands still gets its 10 results.  Everything not said here is smatrix_cf_recommend_sim's contract,
+ * word for word: sessions, first positions, candidates, the score of a pair, weights, exclusion lists, the deny bitmap, tiers, locks,
+ * the mirror, streams, scratch, k <= 64.
+ *   group_of   one uint32 per id 0 .. group_n - 1, group_n <= 2^32: candidate b belongs to group group_of[b].  An id >= group_n, or
+ *              one whose entry is SMATRIX_GROUP_NONE, is UNGROUPED: it is never capped and consumes nobody's quota.  Every other
+ *              32-bit value is a group id, 0 and 0xFFFFFFFE included.
+ *   cap        1 <= cap <= 64: the most results of one session that may share a group.  One number for the call.
+ *   result     walk the session's candidates that are left in the sim call's result order (score descending, equal scores by
+ *              ascending id); take a candidate iff it is ungrouped or fewer than cap candidates already taken share its group; stop
+ *              at k.  ids / scores hold the taken ones in walk order, each score the sim call's bytes for that id; counts[s] is
+ *              their number, which may be < k although the session has >= k candidates.  In closed form: a grouped candidate
+ *              survives iff fewer than cap candidates of its own group precede it in the result order, and the result is the first k
+ *              survivors.  A session item, an excluded id and a denied id are no candidates: they consume no quota.
+ *   unused     entries beyond counts[s]: the host flavour zero-fills them, _dev leaves them.
+ *   no grouping group_of NULL with group_n == 0 writes smatrix_cf_recommend_sim's bytes through the same launches; so does a cap >= k
+ *              with a map given (such a quota refuses nobody before the cut).
+ * Deterministic: the same contents and input give the same bytes; nothing depends on slot order, lane order or the tier.
+ * Cost beyond the sim call's: one 4-byte gather from group_of per candidate, then rounds over the session's table -- a round looks at
+ * the 64 best candidates still alive, takes what the quotas allow and strikes out those 64 and every candidate of a group that is
+ * full now.  A round's first candidate is always taken: at most k rounds, one or two for a typical session.  A session of the
+ * global tier is ended by one workgroup over its whole table (as smatrix_cf_rank's).  The host flavour stages group_of once per call.
+ * Returns -1 for smatrix_cf_recommend_sim's refusals, word for word, and for cap == 0, cap > 64, group_n > 2^32 and group_of NULL
+ * with group_n != 0 (before the device is touched, outputs as they were, both flavours).  0 otherwise.
+ * Not here: a cap per group (an array of quotas), a back-fill that knows the quotas (smatrix_cf_recommend_fill under caps), and the
+ * sharded matrix. */
+#define SMATRIX_GROUP_NONE 0xFFFFFFFFu
+int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                 const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                                 const uint32_t* deny_bits, uint64_t deny_n, const uint32_t* group_of, uint64_t group_n,
+                                 uint32_t cap, int sim, double shrink, uint32_t k, uint32_t* ids, double* scores,
+                                 uint32_t* counts);
+int smatrix_cf_recommend_grouped_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                     const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                     const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_group_of, uint64_t group_n,
+                                     uint32_t cap, int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores,
+                                     uint32_t* d_counts, void* hip_stream);
+
 /* The rank of given items in a session's ranking: where a held-out item lands among ALL the session's candidates, not only among
  * the k <= 64 best -- what hit-rate@k, MRR and the loss of a truncated copy are computed from.  Everything up to and including
  * shrink is smatrix_cf_recommend_sim's contract, word for word: sessions, first positions, candidates, the score of a pair, weights,

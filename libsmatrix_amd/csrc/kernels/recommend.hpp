@@ -24,6 +24,8 @@
 // smatrix_cf_rank (RecRank; k_rec_lds_rank<F>, k_rec_lds_rank_sim<F>, k_rec_gl_rank): the same tables with another ending.  Instead
 // of the k best slots, the session's targets are looked up in the finished table (they are never entered: tiers and table sizes
 // are the recommend call's) and the candidates that beat each are counted, rec_rank_table: one pass over the table per 64 targets.
+// smatrix_cf_recommend_grouped (RecGroup; k_rec_lds_grouped<F>, k_rec_lds_grouped_sim<F>, k_rec_gl_grouped): the same tables with a
+// third ending, rec_group_table: at most cap results of one group, decided in rounds over the 64 best slots still alive.
 // smatrix_cf_recommend_fill (k_rec_fill, at the end of this file): the sim call's launches as they are, and one more behind them that
 // fills the free places of a short result from the caller's list under the session's own filters.
 
@@ -194,6 +196,153 @@ __device__ __forceinline__ void rec_rank_table(const uint32_t* keys, const doubl
   }
 }
 
+// what smatrix_cf_recommend_grouped adds: candidate b belongs to group of[b]; an id >= n, or one whose entry is REC_GROUP_NONE, is
+// ungrouped.  At most cap results of a session share a group
+constexpr uint32_t REC_GROUP_NONE = 0xffffffffu;
+struct RecGroup {
+  const uint32_t* of;
+  uint64_t n;
+  uint32_t cap;
+};
+// the LDS words the grouped ending needs beside the table: NW lists of 64 {key, id, group}, the <= 64 groups a round fills, and
+// {the round's verdict, the key and the id of the last candidate it looked at}
+constexpr uint32_t REC_GRP_DONE = 0xffffffffu;
+constexpr uint32_t rec_group_words(uint32_t NW) { return NW * 64 * 4 + 64 + 4; }
+
+// cf_sort64 / cf_merge_stages in CfById's order with their stage loops kept ROLLED.  Unrolled, every stage's lane masks are loop
+// invariants that are kept in scalar registers across the rounds -- more of them than there are, beside the grouped ending's own state
+// --; rolled, a stage's mask lives for that stage, and the distance of the shuffle is a register, not a constant.
+__device__ __forceinline__ void rec_merge_rolled(CfCand& v, uint32_t lane) {
+  const CfById better;
+#pragma nounroll
+  for (uint32_t j = 32; j; j >>= 1) {
+    const CfCand o = cf_shfl_xor(v, (int)j);
+    if (better(o, v) == ((lane & j) == 0)) v = o;                   // the lower lane of a pair keeps the better one
+  }
+}
+__device__ __forceinline__ void rec_sort64_rolled(CfCand& v, uint32_t lane) {
+  const CfById better;
+#pragma nounroll
+  for (uint32_t k2 = 2; k2 <= 64; k2 <<= 1) {
+#pragma nounroll
+    for (uint32_t j = k2 >> 1; j; j >>= 1) {
+      const CfCand o = cf_shfl_xor(v, (int)j);
+      const bool down = (lane & k2) == 0 || k2 == 64;               // blocks alternate direction; the last pass is best-first
+      if (better(o, v) == (((lane & j) == 0) == down)) v = o;
+    }
+  }
+}
+
+// The grouped ending of both tiers, run by a workgroup of NW waves over the finished table {keys, sq, sum} of tsize slots (a power of
+// two >= 64) of session s: the first k candidates, in CfById's order, that fewer than cap candidates of their own group precede.
+// The candidate test is folded into the sums first (a slot that is no candidate, an empty one included, gets the sum -1.0: "dead"),
+// then sq is free and its first 4 * tsize bytes hold the group of every slot alive -- one gather from gr.of per candidate.
+// A ROUND: the 64 best slots alive (every wave over its share, k_cf_topk's loop; wave 0 merges the waves' lists through ws) stand in
+// wave 0's lanes in order, the group in CfCand::slot.  Lane i is a survivor iff it is ungrouped or (the results taken so far + the
+// lanes below i) hold fewer than cap of its group: every candidate of a group that came before lane i and is not in one of those two
+// places was a survivor itself while the group was below cap, and dead since.  The survivors are numbered by mbcnt behind the results
+// taken, cut at k, stored, and their groups handed to the lanes that own the new places (the results live in lanes, as in
+// k_rec_fill).  Then everything that can no longer be taken dies in one pass: the slots not worse than the round's last (the 64
+// looked at), and the slots of a group that reached cap in this round.  The call ends at k results or after a round that found
+// fewer than 64 alive.  A round's first candidate is always a survivor (its group would be dead otherwise): at most k rounds.
+// A thread meets the same slots in every pass (p = threadIdx.x + i * NW * 64), so the table needs no barrier of its own; the two
+// barriers of a round order ws.  Nothing depends on slot order: the order is CfById's, and ids are distinct.
+template <uint32_t NW, typename I>
+__device__ __forceinline__ void rec_group_table(const uint32_t* keys, double* sq, double* sum, I tsize, const RecGroup& gr, uint32_t k,
+                                                uint32_t s, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                uint32_t* __restrict__ counts, uint32_t* ws) {
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  constexpr uint32_t NT = NW * 64;
+  const CfById better;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  uint32_t* grp = reinterpret_cast<uint32_t*>(sq);
+  long long* l_key = reinterpret_cast<long long*>(ws);              // (ws is 8-byte aligned)
+  uint32_t* l_id = ws + NT * 2;
+  uint32_t* l_grp = l_id + NT;
+  uint32_t* full = l_grp + NT;
+  uint32_t* ctl = full + 64;
+  for (I p = tid; p < tsize; p += NT)
+    if (!(keys[p] != 0 && sq[p] > 0.0)) sum[p] = -1.0;
+  __syncthreads();                                                  // sq is read: the groups go over it
+  for (I p = tid; p < tsize; p += NT)
+    if (__double_as_longlong(sum[p]) >= 0) grp[p] = keys[p] < gr.n ? gr.of[keys[p]] : REC_GROUP_NONE;
+  uint32_t taken = 0, res_grp = REC_GROUP_NONE;                     // wave 0: the results so far, lane r the group of result r
+  for (;;) {
+    CfCand top{NONE, REC_GROUP_NONE, 0xffffffffu};
+    for (I p = tid; p < tsize; p += NT) {                           // (uniform per wave: tsize is a multiple of 64)
+      const long long sk = __double_as_longlong(sum[p]);
+      CfCand cand{NONE, REC_GROUP_NONE, 0xffffffffu};               // (a dead slot carries no id: nothing orders the dead)
+      if (sk >= 0) { cand.key = sk; cand.slot = grp[p]; cand.id = keys[p]; }
+      const CfCand last = cf_shfl(top, 63);
+      if (!__any(cand.key != NONE && better(cand, last))) continue;
+      rec_sort64_rolled(cand, lane);
+      const CfCand rev = cf_shfl(cand, 63 - (int)lane);
+      if (better(rev, top)) top = rev;
+      rec_merge_rolled(top, lane);
+    }
+    l_key[tid] = top.key;
+    l_id[tid] = top.id;
+    l_grp[tid] = top.slot;
+    __syncthreads();
+    if (w == 0) {
+      for (uint32_t v = 1; v < NW; v++) {
+        const CfCand o{l_key[v * 64 + 63 - lane], l_grp[v * 64 + 63 - lane], l_id[v * 64 + 63 - lane]};
+        if (better(o, top)) top = o;
+        rec_merge_rolled(top, lane);
+      }
+      const bool valid = top.key != NONE;                           // (the valid lanes are the first ones)
+      const uint32_t g = top.slot;                                  // REC_GROUP_NONE in a lane that is not valid
+      uint32_t same = 0;
+#pragma nounroll                                                    // (unrolled, the shuffles become 128 scalar registers)
+      for (uint32_t j = 0; j < 64; j++) {                           // (every lane shuffles)
+        const uint32_t r = (uint32_t)__shfl((int)res_grp, (int)j), o = (uint32_t)__shfl((int)g, (int)j);
+        same += (r == g ? 1u : 0u) + (j < lane && o == g ? 1u : 0u);
+      }
+      const bool grouped = g != REC_GROUP_NONE;
+      const bool ok = valid && (!grouped || same < gr.cap);
+      const uint64_t m = __ballot(ok);
+      const uint32_t place = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const bool take = ok && place < k;
+      if (take) {
+        ids[(uint64_t)s * k + place] = top.id;
+        scores[(uint64_t)s * k + place] = __longlong_as_double(top.key);
+      }
+      const uint32_t to = take ? place : 0xffffffffu;
+#pragma nounroll
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t o = (uint32_t)__shfl((int)g, (int)j);
+        if ((uint32_t)__shfl((int)to, (int)j) == lane) res_grp = o;
+      }
+      const uint64_t mf = __ballot(take && grouped && same + 1 == gr.cap);   // one lane per group that is full now
+      if ((mf >> lane) & 1) full[__builtin_amdgcn_mbcnt_hi((uint32_t)(mf >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mf, 0u))] = g;
+      const uint32_t room = k - taken, found = (uint32_t)__popcll(m);
+      taken += found < room ? found : room;
+      const bool done = taken >= k || __popcll(__ballot(valid)) < 64;
+      if (lane == 63) {
+        ctl[0] = done ? REC_GRP_DONE : (uint32_t)__popcll(mf);
+        ctl[1] = (uint32_t)top.key;
+        ctl[2] = (uint32_t)((unsigned long long)top.key >> 32);
+        ctl[3] = top.id;
+      }
+    }
+    __syncthreads();
+    const uint32_t nf = ctl[0];
+    if (nf == REC_GRP_DONE) break;
+    const long long lk = (long long)(((unsigned long long)ctl[2] << 32) | ctl[1]);
+    const uint32_t li = ctl[3];
+    for (I p = tid; p < tsize; p += NT) {
+      const long long sk = __double_as_longlong(sum[p]);
+      if (sk < 0) continue;
+      bool dead = sk > lk || (sk == lk && keys[p] <= li);           // not worse than the round's last: looked at
+      const uint32_t g = grp[p];
+      for (uint32_t c = 0; c < nf; c++) dead |= full[c] == g;       // (an ungrouped slot's REC_GROUP_NONE is never in the list)
+      if (dead) sum[p] = -1.0;
+    }
+  }
+  if (tid == 0) counts[s] = taken;
+  __syncthreads();                                                  // before ws or the table is written again
+}
+
 // ---- tiers ----------------------------------------------------------------------------------------------------------------
 // bound = the sum of the row sizes (slots) of the session's DISTINCT items: every candidate is a non-empty cell of one of
 // those rows, whatever quirk the row carries.  Duplicates are found exactly for sessions of up to REC_DEDUP_MAX items
@@ -262,13 +411,14 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 
 // ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
 // (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's; R: smatrix_cf_rank's ending in place
-// of the top-k, k_rec_lds_rank<F> and k_rec_lds_rank_sim<F>: scores and counts are then the targets' and the candidate counts)
-template <bool F, bool S, bool R>
+// of the top-k, k_rec_lds_rank<F> and k_rec_lds_rank_sim<F>: scores and counts are then the targets' and the candidate counts;
+// G: smatrix_cf_recommend_grouped's ending, rec_group_table, k_rec_lds_grouped<F> and k_rec_lds_grouped_sim<F>)
+template <bool F, bool S, bool R, bool G = false>
 __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
                                         const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
                                         uint32_t* __restrict__ ids, double* __restrict__ scores, uint32_t* __restrict__ counts,
-                                        const RecFilt& f, const RecRank& rk) {
+                                        const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{}) {
   __shared__ uint32_t s_key[REC_LDS_SLOTS];
   __shared__ double s_sq[REC_LDS_SLOTS];
   __shared__ double s_sum[REC_LDS_SLOTS];
@@ -349,6 +499,11 @@ __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* a
       rec_rank_table<true, NW>(s_key, s_sq, s_sum, tsize, rk, s, counts, reinterpret_cast<uint32_t*>(s_sq));
       continue;                                                     // (its last barrier stands before the next session's clearing)
     }
+    if (G) {
+      // the table must outlive the rounds: the groups take the first 16 KiB of s_sq, the waves' lists lie in the rest of it
+      rec_group_table<NW>(s_key, s_sq, s_sum, tsize, gr, k, s, ids, scores, counts, reinterpret_cast<uint32_t*>(s_sq) + REC_LDS_SLOTS);
+      continue;
+    }
     // the k best: every wave over its 64-slot steps (k_cf_topk's loop), then wave 0 merges the waves' lists
     CfCand top{NONE, 0xffffffffu, 0xffffffffu};
     for (uint32_t p0 = w * 64; p0 < tsize; p0 += REC_LDS_THREADS) {
@@ -416,6 +571,25 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_rank_sim(DirSlot* d
                                                                       const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
                                                                       RecRank rk, uint32_t* __restrict__ ncand, RecFilt f) {
   rec_lds<F, true, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, 0u, nullptr, nullptr, ncand, f, rk);
+}
+
+// smatrix_cf_recommend_grouped's instances: the same fill, rec_group_table at the end
+static_assert(REC_LDS_SLOTS * 4 + rec_group_words(REC_LDS_THREADS / 64) * 4 <= REC_LDS_SLOTS * 8, "the groups and the lists share s_sq");
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_grouped(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                     const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                     const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                     uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                     uint32_t* __restrict__ counts, RecFilt f, RecGroup gr) {
+  rec_lds<F, false, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{}, gr);
+}
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_grouped_sim(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                         const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                         uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                         uint32_t* __restrict__ counts, RecFilt f, RecGroup gr) {
+  rec_lds<F, true, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{}, gr);
 }
 
 // ---- global tier -----------------------------------------------------------------------------------------------------------
@@ -647,6 +821,20 @@ __global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_rank(RecGl R, RecR
     if (!rec_in_group(R, idx, &loc)) continue;
     const uint32_t s = R.big_list[idx];
     rec_rank_table<false, NW>(R.gk + loc, R.gq + loc, R.gs + loc, 1ull << R.tlg[s], rk, s, ncand, part);
+  }
+}
+
+// smatrix_cf_recommend_grouped's ending of the global tier, in place of k_rec_gl_topk + k_rec_gl_merge (a segment's 64 best may all be
+// of one group): a workgroup per session of the group over its whole table, gq reused for the groups -- k_rec_gl_rank's shape
+__global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_grouped(RecGl R, RecGroup gr, uint32_t k, uint32_t* __restrict__ ids,
+                                                                      double* __restrict__ scores, uint32_t* __restrict__ counts) {
+  constexpr uint32_t NW = REC_MERGE_THREADS / 64;
+  __shared__ __attribute__((aligned(8))) uint32_t ws[rec_group_words(NW)];
+  for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
+    uint64_t loc;
+    if (!rec_in_group(R, idx, &loc)) continue;
+    const uint32_t s = R.big_list[idx];
+    rec_group_table<NW>(R.gk + loc, R.gq + loc, R.gs + loc, 1ull << R.tlg[s], gr, k, s, ids, scores, counts, ws);
   }
 }
 

@@ -1,5 +1,6 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
-// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev and smatrix_cf_rank / _dev), host side.
+// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_grouped / _dev and smatrix_cf_rank / _dev),
+// host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -25,6 +26,9 @@
 // stands for k_rec_lds, and k_rec_gl_rank for k_rec_gl_topk + k_rec_gl_merge; everything before the ending is shared.
 // The fill call (smatrix_cf_recommend_fill / _dev) is the sim call with ONE launch behind the driver's, rec_fill: k_rec_fill reads
 // the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).
+// The grouped call (smatrix_cf_recommend_grouped / _dev) is the sim call with a third ending (rec_run<.., .., false, true>, RecGroup):
+// k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk + k_rec_gl_merge.  With no map, or a quota that
+// cannot bind (cap >= k), it IS the sim call.
 
 namespace {
 
@@ -53,6 +57,7 @@ struct RecScratch {
   DevBuf<uint64_t> h_opoff;                          // ... and the old import's: the ops before every session
   DevBuf<uint64_t> h_foff;                           // ... and the fill call's: the staged list (one list: two offsets), n_scored
   DevBuf<uint32_t> h_fill, h_nsc;
+  DevBuf<uint32_t> h_grp;                            // ... and the grouped call's: the group of every id
   DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
   DevBuf<unsigned long long> p_keys, p_out;          // directory slot, the n keys collected (ids: h_ids, totals: h_counts, n: h_nsc)
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
@@ -61,7 +66,7 @@ struct RecScratch {
   void for_each_buf(Fn f) {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
-    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(p_ctl); f(p_keys); f(p_out);
+    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(h_grp); f(p_ctl); f(p_keys); f(p_out);
   }
 };
 
@@ -187,9 +192,11 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
 // a bad weight, 0 otherwise.
 // R: the ending is the rank call's, not the top-k: rk's answers are filled and written, d_counts receives the candidate counts,
 // k / d_ids / d_scores are not used
-template <bool F, bool S, bool R>
+// Q: the ending is the grouped call's (R is false): k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk +
+// k_rec_gl_merge, over the map and the quota in gr
+template <bool F, bool S, bool R, bool Q = false>
 int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, const RecRank& rk) {
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{}) {
   DirSlot* dir = m->d_dir;
   const uint32_t dmask = m->dir_size - 1;
   if (R) hipLaunchKernelGGL(k_rec_rank_fill, dim3(1024), dim3(256), 0, s, n, rk);
@@ -205,6 +212,9 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   if (c.n_lds && R)
     hipLaunchKernelGGL(S ? k_rec_lds_rank_sim<F> : k_rec_lds_rank<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
                        dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, rk, d_counts, f);
+  else if (c.n_lds && Q)
+    hipLaunchKernelGGL(S ? k_rec_lds_grouped_sim<F> : k_rec_lds_grouped<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
+                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f, gr);
   else if (c.n_lds)
     hipLaunchKernelGGL(S ? k_rec_lds_sim<F> : k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
                        x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
@@ -215,7 +225,7 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   const uint64_t nseg = cap / REC_SEG;
   const uint32_t np = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.max_len, REC_PLAN_MAX / c.n_big));
   x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big);
-  if (!R) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
+  if (!R && !Q) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
   x.cnt.need((uint64_t)np * c.n_big); x.scan.need((uint64_t)np * c.n_big + 1);
   RecGl G{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
   for (uint64_t g = 0; g < ngroups; g++) {
@@ -241,6 +251,9 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
     }
     if (R) {
       hipLaunchKernelGGL(k_rec_gl_rank, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, rk, d_counts);
+    } else if (Q) {
+      hipLaunchKernelGGL(k_rec_gl_grouped, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, gr, k, d_ids, d_scores,
+                         d_counts);
     } else {
       hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, G, nseg, k, x.lk.p,
                          x.li.p);
@@ -265,12 +278,27 @@ bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
 bool rec_fill_args_ok(const void* fill_ids, uint64_t n_fill, const void* n_scored) {
   return n_scored && n_fill < (1ull << 32) && (fill_ids || n_fill == 0);
 }
+// ... and the grouped call on top of the sim call's
+bool rec_group_args_ok(const void* group_of, uint64_t group_n, uint32_t cap) {
+  return cap != 0 && cap <= 64 && group_n <= (1ull << 32) && (group_of || group_n == 0);
+}
+// does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k:
+// both are the sim call, through its own launches
+bool rec_group_binds(const RecGroup& gr, uint32_t k) { return gr.n != 0 && gr.cap < k; }
 // (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
 
-// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending
+// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending;
+// gr: the grouped ending (never with R)
 template <bool R>
 int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim, const RecRank& rk) {
+                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim, const RecRank& rk,
+                 const RecGroup* gr = nullptr) {
+  if constexpr (!R) {
+    if (gr && sim) return rec_filt_any(f) ? rec_run<true, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
+                                          : rec_run<false, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr);
+    if (gr) return rec_filt_any(f) ? rec_run<true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
+                                   : rec_run<false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr);
+  }
   if (sim) return rec_filt_any(f) ? rec_run<true, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
                                   : rec_run<false, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
   return rec_filt_any(f) ? rec_run<true, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
@@ -293,22 +321,25 @@ void rec_fill(hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* 
 
 // every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
 // f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish.  fl: the fill call, its kernel behind
-// the driver's
+// the driver's; gr: the grouped call, its ending in place of the top-k
 template <bool R>
 int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream, const RecFill* fl = nullptr) {
+            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream, const RecFill* fl = nullptr,
+            const RecGroup* gr = nullptr) {
   if (n_sessions == 0) return 0;
   RecCall c(self, hip_stream);
-  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk);
+  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk, gr);
   if (fl && rc == 0) rec_fill(c.s, (uint32_t)n_sessions, d_offsets, d_items, k, *fl, d_ids, d_scores, d_counts, f);
   return c.finish(rc);
 }
 
 // the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing);
-// fl: the fill call, with the HOST's list and n_scored -- the list goes through the stager as a list of lists that holds one list
+// fl: the fill call, with the HOST's list and n_scored -- the list goes through the stager as a list of lists that holds one list;
+// gr: the grouped call, with the HOST's map, staged once
 int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                       const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
-                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m, const RecFill* fl = nullptr) {
+                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m, const RecFill* fl = nullptr,
+                      const RecGroup* gr = nullptr) {
   if (n_sessions == 0) return 0;
   const uint64_t n = n_sessions;
   if (!rec_host_weights_ok(weights, offsets, n)) return -1;
@@ -319,7 +350,13 @@ int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offset
   x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
   HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, c.s));              // unused entries read 0, as cf_topk_batch's
   HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, c.s));
-  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{});
+  RecGroup d_gr{};
+  if (gr) {
+    x.h_grp.need(gr->n);
+    HIP_OK(hipMemcpyAsync(x.h_grp.p, gr->of, gr->n * 4, hipMemcpyHostToDevice, c.s));
+    d_gr = RecGroup{x.h_grp.p, gr->n, gr->cap};
+  }
+  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{}, gr ? &d_gr : nullptr);
   if (fl) {
     const uint64_t one_list[2] = {0, fl->n};
     const RecList l = c.stage(1, one_list, fl->ids, x.h_foff, x.h_fill);
@@ -442,6 +479,31 @@ int smatrix_cf_recommend_fill(smatrix_t* self, size_t n_sessions, const uint64_t
   const RecFill fl{fill_ids, n_fill, n_scored};
   return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
                            !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, &fl);
+}
+
+int smatrix_cf_recommend_grouped_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                     const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                     const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_group_of, uint64_t group_n, uint32_t cap,
+                                     int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
+                                     void* hip_stream) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
+  if (!rec_group_args_ok(d_group_of, group_n, cap)) return -1;
+  const RecGroup gr{d_group_of, group_n, cap};
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
+                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
+                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, nullptr,
+                        rec_group_binds(gr, k) ? &gr : nullptr);
+}
+
+int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                                 const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n,
+                                 const uint32_t* group_of, uint64_t group_n, uint32_t cap, int sim, double shrink, uint32_t k, uint32_t* ids,
+                                 double* scores, uint32_t* counts) {
+  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
+  if (!rec_group_args_ok(group_of, group_n, cap)) return -1;
+  const RecGroup gr{group_of, group_n, cap};
+  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
+                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, nullptr, rec_group_binds(gr, k) ? &gr : nullptr);
 }
 
 int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,

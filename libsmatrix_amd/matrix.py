@@ -221,6 +221,44 @@ def _fill_ids(fill):
     return _u32(a)
 
 
+GROUP_NONE = 0xFFFFFFFF                                  # SMATRIX_GROUP_NONE: the entry of an id that belongs to no group
+
+
+def _group_map(group_of):
+    """cf_recommend_grouped's map -> uint32[group_n], or None for no map: None, a flat sequence of integers in 0 .. 2**32 - 1 (entry
+    i the group of id i, GROUP_NONE for none), or a dict {id: group} (the ids not named get GROUP_NONE).  Anything else is a
+    ValueError"""
+    if group_of is None:
+        return None
+    if isinstance(group_of, dict):
+        if not group_of:
+            return None
+        ids, groups = _group_ints(list(group_of.keys())), _group_ints(list(group_of.values()))
+        out = np.full(int(ids.max()) + 1, GROUP_NONE, dtype=np.uint32)
+        out[ids] = groups
+        return out
+    if isinstance(group_of, (str, bytes)) or not hasattr(group_of, "__len__"):
+        raise ValueError("group_of must be None, a sequence of group ids or a dict {id: group}, not %r" % (group_of,))
+    if len(group_of) == 0:
+        return None
+    return _u32(_group_ints(group_of))
+
+
+def _group_ints(values):
+    a = np.asarray(values)
+    if a.ndim != 1 or a.size > 1 << 32 or a.dtype.kind not in "iu":
+        raise ValueError("group_of must hold integers in 0 .. 2**32 - 1, one per id")
+    wide = a.astype(np.int64 if a.dtype.kind == "i" else np.uint64)
+    if (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+        raise ValueError("group_of must hold integers in 0 .. 2**32 - 1")
+    return wide.astype(np.uint32)
+
+
+def _check_cap(cap):
+    if not isinstance(cap, (int, np.integer)) or isinstance(cap, bool) or not 1 <= cap <= 64:
+        raise ValueError("cap must be an integer in 1 .. 64, not %r" % (cap,))
+
+
 def _deny_bitmap(deny):
     """a sequence of ids -> (bitmap uint32[(deny_n + 31) / 32], deny_n = the largest id + 1); (None, 0) for no id"""
     ids = np.unique(_u32(deny))
@@ -522,6 +560,37 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
                                                    fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, fill, sim or shrink")
+
+    def cf_recommend_grouped(self, sessions, k, group_of, cap, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_filtered with at most `cap` results of a session from one group -- brand, category, seller -- (include/
+        smatrix_batch.h smatrix_cf_recommend_grouped), applied on the GPU over the session's whole ranking before the cut at k.
+        group_of: a uint32 sequence, entry i the group of id i (GROUP_NONE: none; ids beyond its end: none), or a dict {id: group},
+        or None for no grouping; cap: 1 .. 64.  A candidate is taken iff it is ungrouped or fewer than cap candidates of its group
+        come before it in the ranking.  -> (ids[n,k], scores[n,k] float64, counts[n]); counts[s] may be < k although the session
+        has k candidates and more"""
+        _check_k(k)
+        _check_cap(cap)
+        groups = _group_map(group_of)
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        ids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_grouped(*sess, *filt, _p(groups), 0 if groups is None else int(groups.size), int(cap), *measure,
+                                                        k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
+            raise ValueError("smatrix_cf_recommend_grouped: bad k, n_sessions, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
+        return ids, scores, counts
+
+    def cf_recommend_grouped_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n, cap,
+                                 sim, shrink, k, ids_ptr, scores_ptr, cnt_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given): cf_recommend_sim_dev's, and group uint32[group_n]
+        (None with group_n 0: no grouping)"""
+        _check_k(k)
+        _check_cap(cap)
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_grouped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
+                                                      group_ptr, group_n, int(cap), code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_grouped_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
 
     def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """where given items land in each session's ranking (include/smatrix_batch.h smatrix_cf_rank): cf_recommend_filtered's
