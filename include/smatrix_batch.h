@@ -229,6 +229,37 @@ int smatrix_cf_recommend_grouped_dev(smatrix_t* self, size_t n_sessions, const u
                                      uint32_t cap, int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores,
                                      uint32_t* d_counts, void* hip_stream);
 
+/* A long ranked list: smatrix_cf_recommend_sim with up to SMATRIX_DEEP_MAX results per session -- the candidate stage in front of a
+ * second-stage ranker, a re-ranking by price or margin on the caller's side, recall@k beyond 64 from one call.  Everything is
+ * smatrix_cf_recommend_sim's contract, word for word, except the bound on k: sessions, first positions, candidates, the score of a
+ * pair, weights, exclusion lists, the deny bitmap, the result order (score descending, equal scores by ascending id), tiers, locks,
+ * the mirror, streams, scratch; the host flavour zero-fills the entries beyond counts[s], _dev leaves them.
+ *   k          1 <= k <= SMATRIX_DEEP_MAX.  ids and scores hold n_sessions * k entries (the product is taken in 64 bits); session
+ *              s's are [s*k, s*k + counts[s]), counts[s] = min(k, the candidates left).
+ *   k <= 64    the call IS smatrix_cf_recommend_sim: the same launches, the same bytes in all three outputs.
+ *   k > 64     entry r < 64 of a session has the bytes smatrix_cf_recommend_sim with k = 64 writes there, and for every r
+ *              smatrix_cf_rank with the same arguments answers the target ids[s*k + r] with the rank r and the bytes of
+ *              scores[s*k + r].
+ * Deterministic: the same contents and input give the same bytes; nothing depends on slot order, lane order, the tier or the number of
+ * passes a selection took.
+ * Cost beyond the sim call's, with k > 64: per session a radix select of the k-th best (score, id) over its table -- a pass per byte
+ * in which the candidates' keys still differ, at most 12, each a pass over the table --, then a sort of the <= 1024 entries at or
+ * above it.  A session of the global tier is ended by one workgroup over its whole table (as smatrix_cf_rank's).
+ * Returns -1 for smatrix_cf_recommend_sim's refusals, word for word but for the bound on k, and for k == 0 and k > SMATRIX_DEEP_MAX
+ * (both flavours before the device is touched, outputs as they were; a bad weight as there).  0 otherwise.
+ * Not here: fill lists and group quotas beyond 64 results (smatrix_cf_recommend_fill and smatrix_cf_recommend_grouped keep a
+ * session's results in the 64 lanes of a wave), the item-neighbour calls (smatrix_cf_topk_batch stays at k <= 64), and the sharded
+ * matrix. */
+#define SMATRIX_DEEP_MAX 1024u
+int smatrix_cf_recommend_deep(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                              const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                              const uint32_t* deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* ids,
+                              double* scores, uint32_t* counts);
+int smatrix_cf_recommend_deep_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                  const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k,
+                                  uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream);
+
 /* The rank of given items in a session's ranking: where a held-out item lands among ALL the session's candidates, not only among
  * the k <= 64 best -- what hit-rate@k, MRR and the loss of a truncated copy are computed from.  Everything up to and including
  * shrink is smatrix_cf_recommend_sim's contract, word for word: sessions, first positions, candidates, the score of a pair, weights,

@@ -26,6 +26,8 @@
 // are the recommend call's) and the candidates that beat each are counted, rec_rank_table: one pass over the table per 64 targets.
 // smatrix_cf_recommend_grouped (RecGroup; k_rec_lds_grouped<F>, k_rec_lds_grouped_sim<F>, k_rec_gl_grouped): the same tables with a
 // third ending, rec_group_table: at most cap results of one group, decided in rounds over the 64 best slots still alive.
+// smatrix_cf_recommend_deep with k > 64 (k_rec_lds_deep<F>, k_rec_lds_deep_sim<F>, k_rec_gl_deep): the same tables with a fourth ending,
+// rec_deep_table: up to REC_DEEP_MAX results, by a radix select of the k-th best key and a workgroup sort of what is at or above it.
 // smatrix_cf_recommend_fill (k_rec_fill, at the end of this file): the sim call's launches as they are, and one more behind them that
 // fills the free places of a short result from the caller's list under the session's own filters.
 
@@ -343,6 +345,158 @@ __device__ __forceinline__ void rec_group_table(const uint32_t* keys, double* sq
   __syncthreads();                                                  // before ws or the table is written again
 }
 
+// the LDS words the deep ending needs beside the table: the list of REC_DEEP_MAX {8-byte key, 4-byte id}, the select's 256 bins,
+// and {candidates, collected, the pass's digit, what is still wanted of its bin, the bin's count, -, the OR of the keys (3 words),
+// the OR of their complements (3 words)}
+constexpr uint32_t REC_DEEP_MAX = 1024;       // SMATRIX_DEEP_MAX
+constexpr uint32_t REC_DEEP_CTL = 12;
+constexpr uint32_t rec_deep_words() { return REC_DEEP_MAX * 3 + 256 + REC_DEEP_CTL; }
+
+// The deep ending of both tiers (smatrix_cf_recommend_deep with k > 64), run by a workgroup of NW waves over the finished table
+// {keys, sq, sum} of tsize slots (a power of two >= 64) of session s: the first k <= REC_DEEP_MAX candidates in CfById's order.
+//   1. The candidate test is folded into the sums (a slot that is no candidate, an empty one included, gets the sum -1.0); sq is not
+//      read again, so ws may lie in it.  The candidates are counted and their keys' OR and AND taken: a key is RkCosine's (kernels/
+//      rank_key.hpp), {the sum's bit pattern, 0xFFFFFFFF - id} -- larger is better, which is CfById's order, and unique in a table.
+//   2. With more than k candidates: an MSB radix select of the k-th best key.  It starts at the highest digit in which the keys
+//      differ (RkCosine::start).  A pass counts, in 256 bins, the digit of every key that agrees with the prefix chosen so far; wave
+//      0 walks the bins from the top to the one that holds the `need`-th key, which becomes the next digit of the prefix.  When
+//      that bin is wanted WHOLE (need == its count; at the last digit a bin holds one key) the select ends: the threshold is the
+//      prefix with zeros below, and exactly k keys are at or above it.  At most 12 passes; a table without ties across the cut ends
+//      within the score's digits.  With at most k candidates the threshold is RkCosine::zero(): everything.
+//   3. The slots at or above the threshold go into the list in any order (a wave's share behind one atomic), the list is padded to
+//      a power of two with the worst key, sorted by a bitonic network over LDS (a pair per thread and step) and stored, a thread
+//      per place.  Keys are unique, so the sorted list does not depend on the order of collection.
+// A thread meets the same slots in every pass (p = threadIdx.x + i * NW * 64), so the folded sums need no barrier of their own.
+template <uint32_t NW, typename I>
+__device__ __forceinline__ void rec_deep_table(const uint32_t* keys, const double* sq, double* sum, I tsize, uint32_t k, uint32_t s,
+                                               uint32_t* __restrict__ ids, double* __restrict__ scores, uint32_t* __restrict__ counts,
+                                               uint32_t* ws) {
+  constexpr long long NONE = (long long)0x8000000000000000ull;
+  constexpr uint32_t NT = NW * 64;
+  typedef RkCosine RK;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  long long* l_key = reinterpret_cast<long long*>(ws);              // (ws is 8-byte aligned)
+  uint32_t* l_id = ws + REC_DEEP_MAX * 2;
+  uint32_t* hist = l_id + REC_DEEP_MAX;
+  uint32_t* ctl = hist + 256;
+  uint32_t mine = 0;
+  RK::Acc acc = RK::acc0();
+  for (I p = tid; p < tsize; p += NT) {
+    const uint32_t b = keys[p];
+    if (b != 0 && sq[p] > 0.0) {
+      mine++;
+      RK::acc_add(acc, RK::make(b, (uint64_t)__double_as_longlong(sum[p])));
+    } else {
+      sum[p] = -1.0;
+    }
+  }
+  __syncthreads();                                                  // sq is read: ws may lie in it
+  if (tid < REC_DEEP_CTL) ctl[tid] = 0;
+  __syncthreads();
+  for (uint32_t d = 32; d; d >>= 1) {
+    mine += (uint32_t)__shfl_xor((int)mine, (int)d);
+#pragma unroll
+    for (uint32_t j = 0; j < 6; j++) acc.w[j] |= (uint32_t)__shfl_xor((int)acc.w[j], (int)d);
+  }
+  if (lane == 0) {
+    atomicAdd(&ctl[0], mine);
+#pragma unroll
+    for (uint32_t j = 0; j < 6; j++) atomicOr(&ctl[6 + j], acc.w[j]);
+  }
+  __syncthreads();
+  const uint32_t ncand = ctl[0];
+  const uint32_t want = ncand < k ? ncand : k;
+  RK::Key thr = RK::zero();
+  if (ncand > k) {                                                  // (uniform: two keys and more, and they differ)
+#pragma unroll
+    for (uint32_t j = 0; j < 6; j++) acc.w[j] = ctl[6 + j];
+    uint32_t dg = RK::start(acc, thr), need = k;
+    for (;;) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for (I p = tid; p < tsize; p += NT) {
+        const long long sk = __double_as_longlong(sum[p]);
+        if (sk < 0) continue;
+        const RK::Key key = RK::make(keys[p], (uint64_t)sk);
+        if (RK::agrees_above(key, thr, dg)) atomicAdd(&hist[RK::digit(key, dg)], 1u);
+      }
+      __syncthreads();
+      if (w == 0) {                                                 // lane l: the bins 255 - 4l .. 252 - 4l, from the top
+        const uint32_t top = 255 - 4 * lane;
+        const uint32_t c0 = hist[top], c1 = hist[top - 1], c2 = hist[top - 2], c3 = hist[top - 3];
+        const uint32_t tot = c0 + c1 + c2 + c3;
+        uint32_t incl = tot;
+        for (uint32_t d = 1; d < 64; d <<= 1) {                     // (every lane shuffles)
+          const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
+          if (lane >= d) incl += o;
+        }
+        uint32_t above = incl - tot;                                // the keys in the bins above this lane's
+        if (above < need && need <= incl) {                         // one lane: the pass counted `need` keys and more
+          uint32_t dd = top, c = c0;
+          if (above + c < need) {
+            above += c; dd--; c = c1;
+            if (above + c < need) {
+              above += c; dd--; c = c2;
+              if (above + c < need) { above += c; dd--; c = c3; }
+            }
+          }
+          ctl[2] = dd;
+          ctl[3] = need - above;
+          ctl[4] = c;
+        }
+      }
+      __syncthreads();
+      RK::take_digit(thr, dg, ctl[2]);
+      need = ctl[3];
+      if (need == ctl[4] || dg == 0) break;                         // the bin is wanted whole: every key at or above the prefix
+      dg--;
+    }
+  }
+  for (I p0 = w * 64; p0 < tsize; p0 += NT) {                       // (uniform per wave: tsize is a multiple of 64)
+    const I p = p0 + lane;
+    const long long sk = __double_as_longlong(sum[p]);
+    const uint32_t b = keys[p];
+    const bool take = sk >= 0 && RK::ge(RK::make(b, (uint64_t)sk), thr);
+    const uint64_t m = __ballot(take);
+    if (m == 0) continue;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&ctl[1], (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, 0);
+    const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (take && at < REC_DEEP_MAX) {                                // (at < want <= REC_DEEP_MAX: exactly `want` slots are taken)
+      l_key[at] = sk;
+      l_id[at] = b;
+    }
+  }
+  uint32_t P = 64;
+  while (P < want) P <<= 1;
+  for (uint32_t i = want + tid; i < P; i += NT) { l_key[i] = NONE; l_id[i] = 0xffffffffu; }
+  __syncthreads();
+  const CfById better;
+#pragma nounroll
+  for (uint32_t k2 = 2; k2 <= P; k2 <<= 1) {
+#pragma nounroll
+    for (uint32_t j = k2 >> 1; j; j >>= 1) {
+      for (uint32_t t = tid; t < P / 2; t += NT) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;   // the pair (i, i + j) of step j
+        const CfCand a{l_key[i], 0u, l_id[i]}, c{l_key[o], 0u, l_id[o]};
+        const bool down = (i & k2) == 0;                            // blocks alternate direction; the last pass (k2 == P) is best-first
+        if (better(c, a) == down) {
+          l_key[i] = c.key; l_id[i] = c.id;
+          l_key[o] = a.key; l_id[o] = a.id;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t r = tid; r < want; r += NT) {
+    ids[(uint64_t)s * k + r] = l_id[r];
+    scores[(uint64_t)s * k + r] = __longlong_as_double(l_key[r]);
+  }
+  if (tid == 0) counts[s] = want;
+  __syncthreads();                                                  // before ws or the table is written again
+}
+
 // ---- tiers ----------------------------------------------------------------------------------------------------------------
 // bound = the sum of the row sizes (slots) of the session's DISTINCT items: every candidate is a non-empty cell of one of
 // those rows, whatever quirk the row carries.  Duplicates are found exactly for sessions of up to REC_DEDUP_MAX items
@@ -412,8 +566,9 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 // ---- LDS tier: a workgroup per session ---------------------------------------------------------------------------------------
 // (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's; R: smatrix_cf_rank's ending in place
 // of the top-k, k_rec_lds_rank<F> and k_rec_lds_rank_sim<F>: scores and counts are then the targets' and the candidate counts;
-// G: smatrix_cf_recommend_grouped's ending, rec_group_table, k_rec_lds_grouped<F> and k_rec_lds_grouped_sim<F>)
-template <bool F, bool S, bool R, bool G = false>
+// G: smatrix_cf_recommend_grouped's ending, rec_group_table, k_rec_lds_grouped<F> and k_rec_lds_grouped_sim<F>;
+// D: smatrix_cf_recommend_deep's ending, rec_deep_table, k_rec_lds_deep<F> and k_rec_lds_deep_sim<F>)
+template <bool F, bool S, bool R, bool G = false, bool D = false>
 __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
                                         const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
@@ -504,6 +659,11 @@ __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* a
       rec_group_table<NW>(s_key, s_sq, s_sum, tsize, gr, k, s, ids, scores, counts, reinterpret_cast<uint32_t*>(s_sq) + REC_LDS_SLOTS);
       continue;
     }
+    if (D) {
+      // the table must outlive the select's passes: the list, the bins and the control words lie in s_sq, free once it is folded
+      rec_deep_table<NW>(s_key, s_sq, s_sum, tsize, k, s, ids, scores, counts, reinterpret_cast<uint32_t*>(s_sq));
+      continue;
+    }
     // the k best: every wave over its 64-slot steps (k_cf_topk's loop), then wave 0 merges the waves' lists
     CfCand top{NONE, 0xffffffffu, 0xffffffffu};
     for (uint32_t p0 = w * 64; p0 < tsize; p0 += REC_LDS_THREADS) {
@@ -590,6 +750,25 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_grouped_sim(DirSlot
                                                                          uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
                                                                          uint32_t* __restrict__ counts, RecFilt f, RecGroup gr) {
   rec_lds<F, true, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{}, gr);
+}
+
+// smatrix_cf_recommend_deep's instances (k > 64): the same fill, rec_deep_table at the end
+static_assert(rec_deep_words() * 4 <= REC_LDS_SLOTS * 8, "the list, the bins and the control words share s_sq");
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_deep(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                  const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                  const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                  uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                  uint32_t* __restrict__ counts, RecFilt f) {
+  rec_lds<F, false, false, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{});
+}
+template <bool F>
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_deep_sim(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                      const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                      const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                      uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                      uint32_t* __restrict__ counts, RecFilt f) {
+  rec_lds<F, true, false, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{});
 }
 
 // ---- global tier -----------------------------------------------------------------------------------------------------------
@@ -835,6 +1014,20 @@ __global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_grouped(RecGl R, R
     if (!rec_in_group(R, idx, &loc)) continue;
     const uint32_t s = R.big_list[idx];
     rec_group_table<NW>(R.gk + loc, R.gq + loc, R.gs + loc, 1ull << R.tlg[s], gr, k, s, ids, scores, counts, ws);
+  }
+}
+
+// smatrix_cf_recommend_deep's ending of the global tier (k > 64), in place of k_rec_gl_topk + k_rec_gl_merge (a segment's list holds 64
+// entries): a workgroup per session of the group over its whole table, gq folded into gs first -- k_rec_gl_rank's shape
+__global__ __launch_bounds__(REC_MERGE_THREADS) void k_rec_gl_deep(RecGl R, uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                   uint32_t* __restrict__ counts) {
+  constexpr uint32_t NW = REC_MERGE_THREADS / 64;
+  __shared__ __attribute__((aligned(8))) uint32_t ws[rec_deep_words()];
+  for (uint32_t idx = blockIdx.x; idx < R.n_big; idx += gridDim.x) {
+    uint64_t loc;
+    if (!rec_in_group(R, idx, &loc)) continue;
+    const uint32_t s = R.big_list[idx];
+    rec_deep_table<NW>(R.gk + loc, R.gq + loc, R.gs + loc, 1ull << R.tlg[s], k, s, ids, scores, counts, ws);
   }
 }
 

@@ -1,6 +1,6 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
-// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_grouped / _dev and smatrix_cf_rank / _dev),
-// host side.
+// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_grouped / _dev,
+// smatrix_cf_recommend_deep / _dev and smatrix_cf_rank / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -29,6 +29,9 @@
 // The grouped call (smatrix_cf_recommend_grouped / _dev) is the sim call with a third ending (rec_run<.., .., false, true>, RecGroup):
 // k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk + k_rec_gl_merge.  With no map, or a quota that
 // cannot bind (cap >= k), it IS the sim call.
+// The deep call (smatrix_cf_recommend_deep / _dev) is the sim call with k up to SMATRIX_DEEP_MAX and, above 64, a fourth ending
+// (rec_run<.., .., false, false, true>): k_rec_lds_deep stands for k_rec_lds, and k_rec_gl_deep for k_rec_gl_topk + k_rec_gl_merge (lk / li
+// are not allocated).  With k <= 64 it IS the sim call.
 
 namespace {
 
@@ -194,7 +197,9 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
 // k / d_ids / d_scores are not used
 // Q: the ending is the grouped call's (R is false): k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk +
 // k_rec_gl_merge, over the map and the quota in gr
-template <bool F, bool S, bool R, bool Q = false>
+// D: the ending is the deep call's (R and Q are false; k may be up to SMATRIX_DEEP_MAX): k_rec_lds_deep stands for k_rec_lds, and
+// k_rec_gl_deep for k_rec_gl_topk + k_rec_gl_merge
+template <bool F, bool S, bool R, bool Q = false, bool D = false>
 int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
             uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{}) {
   DirSlot* dir = m->d_dir;
@@ -215,6 +220,9 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   else if (c.n_lds && Q)
     hipLaunchKernelGGL(S ? k_rec_lds_grouped_sim<F> : k_rec_lds_grouped<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
                        dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f, gr);
+  else if (c.n_lds && D)
+    hipLaunchKernelGGL(S ? k_rec_lds_deep_sim<F> : k_rec_lds_deep<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
+                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
   else if (c.n_lds)
     hipLaunchKernelGGL(S ? k_rec_lds_sim<F> : k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
                        x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
@@ -225,7 +233,7 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   const uint64_t nseg = cap / REC_SEG;
   const uint32_t np = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.max_len, REC_PLAN_MAX / c.n_big));
   x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big);
-  if (!R && !Q) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
+  if (!R && !Q && !D) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
   x.cnt.need((uint64_t)np * c.n_big); x.scan.need((uint64_t)np * c.n_big + 1);
   RecGl G{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
   for (uint64_t g = 0; g < ngroups; g++) {
@@ -254,6 +262,8 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
     } else if (Q) {
       hipLaunchKernelGGL(k_rec_gl_grouped, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, gr, k, d_ids, d_scores,
                          d_counts);
+    } else if (D) {
+      hipLaunchKernelGGL(k_rec_gl_deep, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, k, d_ids, d_scores, d_counts);
     } else {
       hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, G, nseg, k, x.lk.p,
                          x.li.p);
@@ -285,15 +295,23 @@ bool rec_group_args_ok(const void* group_of, uint64_t group_n, uint32_t cap) {
 // does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k:
 // both are the sim call, through its own launches
 bool rec_group_binds(const RecGroup& gr, uint32_t k) { return gr.n != 0 && gr.cap < k; }
+// what the deep call refuses in place of the sim call's k <= 64, and when its own ending runs: up to 64 results it IS the sim call
+bool rec_deep_k_ok(uint32_t k) { return k != 0 && k <= SMATRIX_DEEP_MAX; }
+bool rec_deep_binds(uint32_t k) { return k > 64; }
+static_assert(SMATRIX_DEEP_MAX == REC_DEEP_MAX, "the list of kernels/recommend.hpp holds SMATRIX_DEEP_MAX entries");
 // (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
 
 // the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending;
-// gr: the grouped ending (never with R)
+// gr: the grouped ending (never with R); deep: the deep ending (never with R or gr)
 template <bool R>
 int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
                  uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim, const RecRank& rk,
-                 const RecGroup* gr = nullptr) {
+                 const RecGroup* gr = nullptr, bool deep = false) {
   if constexpr (!R) {
+    if (deep && sim) return rec_filt_any(f) ? rec_run<true, true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
+                                            : rec_run<false, true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
+    if (deep) return rec_filt_any(f) ? rec_run<true, false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
+                                     : rec_run<false, false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
     if (gr && sim) return rec_filt_any(f) ? rec_run<true, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
                                           : rec_run<false, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr);
     if (gr) return rec_filt_any(f) ? rec_run<true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
@@ -321,25 +339,25 @@ void rec_fill(hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* 
 
 // every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
 // f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish.  fl: the fill call, its kernel behind
-// the driver's; gr: the grouped call, its ending in place of the top-k
+// the driver's; gr: the grouped call, its ending in place of the top-k; deep: the deep call with k > 64, its ending in that place
 template <bool R>
 int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
             uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream, const RecFill* fl = nullptr,
-            const RecGroup* gr = nullptr) {
+            const RecGroup* gr = nullptr, bool deep = false) {
   if (n_sessions == 0) return 0;
   RecCall c(self, hip_stream);
-  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk, gr);
+  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk, gr, deep);
   if (fl && rc == 0) rec_fill(c.s, (uint32_t)n_sessions, d_offsets, d_items, k, *fl, d_ids, d_scores, d_counts, f);
   return c.finish(rc);
 }
 
 // the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing);
 // fl: the fill call, with the HOST's list and n_scored -- the list goes through the stager as a list of lists that holds one list;
-// gr: the grouped call, with the HOST's map, staged once
+// gr: the grouped call, with the HOST's map, staged once; deep: the deep call with k > 64 (n * k: 64-bit throughout)
 int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                       const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
                       uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m, const RecFill* fl = nullptr,
-                      const RecGroup* gr = nullptr) {
+                      const RecGroup* gr = nullptr, bool deep = false) {
   if (n_sessions == 0) return 0;
   const uint64_t n = n_sessions;
   if (!rec_host_weights_ok(weights, offsets, n)) return -1;
@@ -356,7 +374,7 @@ int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offset
     HIP_OK(hipMemcpyAsync(x.h_grp.p, gr->of, gr->n * 4, hipMemcpyHostToDevice, c.s));
     d_gr = RecGroup{x.h_grp.p, gr->n, gr->cap};
   }
-  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{}, gr ? &d_gr : nullptr);
+  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{}, gr ? &d_gr : nullptr, deep);
   if (fl) {
     const uint64_t one_list[2] = {0, fl->n};
     const RecList l = c.stage(1, one_list, fl->ids, x.h_foff, x.h_fill);
@@ -504,6 +522,25 @@ int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint6
   const RecGroup gr{group_of, group_n, cap};
   return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
                            !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, nullptr, rec_group_binds(gr, k) ? &gr : nullptr);
+}
+
+int smatrix_cf_recommend_deep_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                  const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* d_ids,
+                                  double* d_scores, uint32_t* d_counts, void* hip_stream) {
+  if (!sim_args_ok(sim, shrink) || !rec_deep_k_ok(k) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, 1u)) return -1;
+  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
+                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
+                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, nullptr, nullptr,
+                        rec_deep_binds(k));
+}
+
+int smatrix_cf_recommend_deep(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                              const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
+                              double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts) {
+  if (!sim_args_ok(sim, shrink) || !rec_deep_k_ok(k) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, 1u)) return -1;
+  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
+                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, nullptr, nullptr, rec_deep_binds(k));
 }
 
 int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,

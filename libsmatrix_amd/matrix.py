@@ -259,6 +259,14 @@ def _check_cap(cap):
         raise ValueError("cap must be an integer in 1 .. 64, not %r" % (cap,))
 
 
+DEEP_MAX = 1024                                          # include/smatrix_batch.h SMATRIX_DEEP_MAX
+
+
+def _check_deep_k(k):
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= DEEP_MAX:
+        raise ValueError("k must be an integer in 1 .. %d, not %r" % (DEEP_MAX, k))
+
+
 def _deny_bitmap(deny):
     """a sequence of ids -> (bitmap uint32[(deny_n + 31) / 32], deny_n = the largest id + 1); (None, 0) for no id"""
     ids = np.unique(_u32(deny))
@@ -591,6 +599,32 @@ class SparseMatrix:
         if self._lib.smatrix_cf_recommend_grouped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
                                                       group_ptr, group_n, int(cap), code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
             raise ValueError("smatrix_cf_recommend_grouped_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
+
+    def cf_recommend_deep(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_filtered with up to DEEP_MAX = 1024 results per session (include/smatrix_batch.h smatrix_cf_recommend_deep):
+        the candidates for a second-stage ranker, for re-ranking on the caller's side, for recall@k beyond 64.  Every argument is
+        cf_recommend_filtered's but k, an integer in 1 .. DEEP_MAX.  -> (ids[n,k], scores[n,k] float64, counts[n]) as there: the
+        first 64 entries of a session are cf_recommend_filtered's with k = 64, and cf_rank answers ids[s, r] with the rank r"""
+        _check_deep_k(k)
+        k = int(k)
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        ids = np.zeros((n, k), dtype=np.uint32)
+        scores = np.zeros((n, k), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_deep(*sess, *filt, *measure, k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
+            raise ValueError("smatrix_cf_recommend_deep: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
+        return ids, scores, counts
+
+    def cf_recommend_deep_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, k,
+                              ids_ptr, scores_ptr, cnt_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given): cf_recommend_sim_dev's, with k up to DEEP_MAX;
+        ids uint32[n*k], scores float64[n*k]"""
+        _check_deep_k(k)
+        code, h = _sim(sim), _shrink(shrink)
+        sp = getattr(stream, "cuda_stream", stream)
+        if self._lib.smatrix_cf_recommend_deep_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
+                                                   deny_n, code, h, int(k), ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+            raise ValueError("smatrix_cf_recommend_deep_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
 
     def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """where given items land in each session's ranking (include/smatrix_batch.h smatrix_cf_rank): cf_recommend_filtered's
