@@ -1,37 +1,42 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
-// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_grouped / _dev,
-// smatrix_cf_recommend_deep / _dev and smatrix_cf_rank / _dev), host side.
+// smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_fill / _dev,
+// smatrix_cf_recommend_grouped / _dev, smatrix_cf_recommend_deep / _dev and smatrix_cf_rank / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
-// Three layers, top down:
-//   the extern "C" symbols   refuse bad arguments, then name what the call was given: a RecFilt, a measure, a RecRank
-//   RecCall                  ONE scope for every call on the read path's scratch (the files included behind this one as well: the
-//                            item-neighbour calls' host flavours, the explain call, both imports, the popular call): the matrix lock,
-//                            the scalar mirror written back (cache_sync), the stream, the wait for the call before, and at finish
-//                            the event, the synchronisation rule and the trim.  Its stagers carry a host flavour's arrays to the
-//                            device: stage (a window of a list of lists: sessions, exclusion lists, targets), stage_weights,
-//                            stage_filter.  A _dev flavour is the scope around the driver; a host flavour stages, runs, copies back
-//   rec_run<F, S, R>         the driver, every array on the device:
+// Four layers, top down:
+//   the extern "C" symbols   each is its refusals, its request, the call.  rec_args_ok refuses what every call refuses; a call adds
+//                            its own (rec_k_ok, rec_deep_k_ok, rec_fill_args_ok, rec_group_args_ok, the targets)
+//   RecReq (rec_req)         ONE request: everything a session call is given -- the sessions, the RecFilt, the ending (RecEnd), k and
+//                            the outputs, the RecRank, the RecGroup, the RecFill -- with the arrays where the caller has them.  rec_req
+//                            writes the one RecFilt literal and is the one place that normalises: which ending really runs, and
+//                            which kernel instances
+//   rec_call                 ONE call function for both flavours: scope, (host) rec_stage, rec_run, rec_fill, (host) rec_copy_back,
+//                            finish.  The scope is RecCall, the one for every call on the read path's scratch (the files included
+//                            behind this one as well: the item-neighbour calls' host flavours, the explain call, both imports, the
+//                            popular call): the matrix lock, the scalar mirror written back (cache_sync), the stream, the wait for the
+//                            call before, and at finish the event, the synchronisation rule and the trim.  Its stagers carry a host
+//                            flavour's arrays to the device: stage (a window of a list of lists: sessions, exclusion lists, targets),
+//                            stage_weights, stage_filter
+//   rec_run                  the driver, ONE host function, given a request whose arrays are on the device:
 //     1. k_rec_bound sorts the sessions into the LDS tier and the global tier; ONE read-back of RecCtl (counts, global-tier sizes)
-//     2. k_rec_lds: every LDS-tier session, one workgroup each
+//     2. rec_launch_lds: every LDS-tier session, one workgroup each, by the kernel of the request's ending
 //     3. the global tier, per group of sessions whose tables fit REC_GROUP_SLOTS (normally one group): zeroed tables, k_rec_gl_init,
 //        per block of item positions the chunk counts (k_rec_gl_plan) and their scan, a k_rec_gl_scan launch per position (the
-//        kernel boundary keeps the items in session order), k_rec_gl_topk, k_rec_gl_merge
-// The filtered call runs the kernels' <true> instances for its RecFilt (weights, exclusion lists, deny bitmap); with nothing given
-// it runs the <false> ones, and that is what smatrix_cf_recommend_batch is: the filtered call with nothing given.
-// The sim call is the filtered call with a measure and a shrinkage in the RecFilt and, for the two kernels that make a score,
-// their _sim instances; with SMATRIX_SIM_COSINE and shrink 0 it IS the filtered call.
-// The rank call is the sim call with another ending (rec_run<.., .., true>): the answers are filled with "no answer", k_rec_lds_rank
-// stands for k_rec_lds, and k_rec_gl_rank for k_rec_gl_topk + k_rec_gl_merge; everything before the ending is shared.
+//        kernel boundary keeps the items in session order), then rec_launch_tail: the kernels of the request's ending
+// The endings (RecEnd), each a case of the two launch switches:
+//   TopK     k_rec_lds; k_rec_gl_topk + k_rec_gl_merge (the only ending that uses lk / li)
+//   Rank     the rank call: the answers are filled with "no answer" first (k_rec_rank_fill), k_rec_lds_rank, k_rec_gl_rank; counts
+//            receives the candidate counts, k / ids / scores are not used
+//   Grouped  the grouped call, over the map and the quota of its RecGroup: k_rec_lds_grouped, k_rec_gl_grouped
+//   Deep     the deep call, k up to SMATRIX_DEEP_MAX: k_rec_lds_deep, k_rec_gl_deep
+// Everything before the ending is shared.  A request with something in its RecFilt (weights, exclusion lists, deny bitmap) runs the
+// kernels' <true> instances and with nothing given the <false> ones; with a measure in it the two kernels that make a score run as
+// their _sim instances.  What rec_req makes of the calls, and the header promises: smatrix_cf_recommend_batch is the filtered call
+// with nothing given; the sim call with SMATRIX_SIM_COSINE and shrink 0 IS the filtered call; the grouped call with no map, or with a
+// quota that cannot bind (cap >= k), and the deep call with k <= 64 ARE the sim call, through the same launches.
 // The fill call (smatrix_cf_recommend_fill / _dev) is the sim call with ONE launch behind the driver's, rec_fill: k_rec_fill reads
 // the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).
-// The grouped call (smatrix_cf_recommend_grouped / _dev) is the sim call with a third ending (rec_run<.., .., false, true>, RecGroup):
-// k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk + k_rec_gl_merge.  With no map, or a quota that
-// cannot bind (cap >= k), it IS the sim call.
-// The deep call (smatrix_cf_recommend_deep / _dev) is the sim call with k up to SMATRIX_DEEP_MAX and, above 64, a fourth ending
-// (rec_run<.., .., false, false, true>): k_rec_lds_deep stands for k_rec_lds, and k_rec_gl_deep for k_rec_gl_topk + k_rec_gl_merge (lk / li
-// are not allocated).  With k <= 64 it IS the sim call.
 
 namespace {
 
@@ -190,42 +195,102 @@ void rec_scan(RecScratch& x, hipStream_t s, const uint32_t* in, uint64_t n, uint
   HIP_OK(hipGetLastError());
 }
 
-// the whole call on stream s, every array on the device; returns with the work enqueued (after one synchronising read-back).
-// F: the filtered call with something given in f; S: the sim call, the score is f.m's.  -1 (nothing but k_rec_bound has run) for
-// a bad weight, 0 otherwise.
-// R: the ending is the rank call's, not the top-k: rk's answers are filled and written, d_counts receives the candidate counts,
-// k / d_ids / d_scores are not used
-// Q: the ending is the grouped call's (R is false): k_rec_lds_grouped stands for k_rec_lds, and k_rec_gl_grouped for k_rec_gl_topk +
-// k_rec_gl_merge, over the map and the quota in gr
-// D: the ending is the deep call's (R and Q are false; k may be up to SMATRIX_DEEP_MAX): k_rec_lds_deep stands for k_rec_lds, and
-// k_rec_gl_deep for k_rec_gl_topk + k_rec_gl_merge
-template <bool F, bool S, bool R, bool Q = false, bool D = false>
-int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{}) {
+// what ends a session's table: the top-k, or the rank call's, the grouped call's or the deep call's ending in its place
+enum class RecEnd { TopK, Rank, Grouped, Deep };
+
+// what smatrix_cf_recommend_fill adds to the sim call: the caller's list and where the scored counts go (NULL: not the fill call)
+struct RecFill {
+  const uint32_t* ids;
+  uint64_t n;
+  uint32_t* n_scored;
+};
+
+// Everything a session call is given, once.  The arrays are the caller's, host or device: an entry point writes down what it was
+// handed, rec_stage makes a host flavour's request into one on the device, and the driver only ever sees the latter.
+struct RecReq {
+  uint32_t n;                                 // the sessions: off[0 .. n], items
+  const uint64_t* off;
+  const uint32_t* items;
+  RecFilt f;
+  bool filt, sim;                             // the kernels' instances: <true> for something given in f; _sim: the score is f.m's
+  RecEnd end;
+  uint32_t k;                                 // TopK, Grouped, Deep: ids / scores [n * k]; Rank: 0 and NULL
+  uint32_t* ids;
+  double* scores;
+  uint32_t* counts;                           // [n]; Rank: the candidate counts
+  RecRank rk;                                 // Rank: the target lists and their answers
+  RecGroup gr;                                // Grouped: the map and the quota
+  RecFill fl;                                 // the fill call (fl.n_scored is given): k_rec_fill behind the driver's launches
+};
+
+// does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k
+bool rec_group_binds(const RecGroup& gr, uint32_t k) { return gr.n != 0 && gr.cap < k; }
+
+// The request of a call behind its refusals, normalised HERE and nowhere else.  These are contracts of the header, not shortcuts: a
+// grouped call that cannot bind and a deep call with k <= 64 ARE the sim call, (COSINE, 0) IS the filtered call, and a filtered
+// call with nothing given IS the plain call -- through the same launches, the <false> and the not-_sim instances they always ran.
+// The one RecFilt literal is here too: NULL / 0 for what was not given; the calls without a measure pass SMATRIX_SIM_COSINE and 0.0.
+RecReq rec_req(size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights, const uint64_t* ex_offsets,
+               const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim, double shrink, RecEnd end, uint32_t k, uint32_t* ids,
+               double* scores, uint32_t* counts, const RecRank& rk = RecRank{}, const RecGroup& gr = RecGroup{}, const RecFill& fl = RecFill{}) {
+  const RecFilt f{weights, ex_offsets, ex_items, deny_bits, deny_n, SimArgs{sim, shrink}};
+  if (end == RecEnd::Grouped && !rec_group_binds(gr, k)) end = RecEnd::TopK;
+  if (end == RecEnd::Deep && k <= 64) end = RecEnd::TopK;                 // up to 64 results the top-k ending holds them
+  return RecReq{(uint32_t)n_sessions, offsets, items, f, f.w || f.ex_off || f.deny_n, !sim_is_plain_cosine(sim, shrink), end, k, ids, scores,
+                counts, rk, end == RecEnd::Grouped ? gr : RecGroup{}, fl};
+}
+
+// a kernel template's instance for request q: k<true> with a filter, k<false> without; and of k / k_sim the second for a measure
+#define REC_F(q, k) ((q).filt ? k<true> : k<false>)
+#define REC_FS(q, k) ((q).sim ? REC_F(q, k##_sim) : REC_F(q, k))
+
+// the LDS tier, one workgroup per session of lds_list: the ending's kernel stands for k_rec_lds, behind the arguments all four share
+void rec_launch_lds(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q, uint32_t n_lds) {
+  auto launch = [&](auto kernel, auto... ending) {
+    hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, m->d_dir, m->dir_size - 1, m->arena.base,
+                       x.ctl.p, x.lds_list.p, x.tlg.p, q.off, q.items, ending...);
+  };
+  switch (q.end) {
+    case RecEnd::TopK:    launch(REC_FS(q, k_rec_lds), q.k, q.ids, q.scores, q.counts, q.f); break;
+    case RecEnd::Rank:    launch(REC_FS(q, k_rec_lds_rank), q.rk, q.counts, q.f); break;
+    case RecEnd::Grouped: launch(REC_FS(q, k_rec_lds_grouped), q.k, q.ids, q.scores, q.counts, q.f, q.gr); break;
+    case RecEnd::Deep:    launch(REC_FS(q, k_rec_lds_deep), q.k, q.ids, q.scores, q.counts, q.f); break;
+  }
+}
+
+// the global tier's ending over a group's finished tables G: one workgroup per session -- for the top-k behind a wave per segment
+void rec_launch_tail(RecScratch& x, hipStream_t s, const RecReq& q, const RecGl& G, uint64_t nseg) {
+  auto launch = [&](auto kernel, auto... ending) {
+    hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(G.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, ending...);
+  };
+  switch (q.end) {
+    case RecEnd::TopK:
+      hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, G, nseg, q.k, x.lk.p,
+                         x.li.p);
+      launch(k_rec_gl_merge, q.k, x.lk.p, x.li.p, q.ids, q.scores, q.counts);
+      break;
+    case RecEnd::Rank:    launch(k_rec_gl_rank, q.rk, q.counts); break;
+    case RecEnd::Grouped: launch(k_rec_gl_grouped, q.gr, q.k, q.ids, q.scores, q.counts); break;
+    case RecEnd::Deep:    launch(k_rec_gl_deep, q.k, q.ids, q.scores, q.counts); break;
+  }
+}
+
+// the whole call on stream s, every array of q on the device; returns with the work enqueued (after one synchronising read-back).
+// -1 (nothing but k_rec_bound has run) for a bad weight, which only a request with a filter can have; 0 otherwise.
+int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
   DirSlot* dir = m->d_dir;
-  const uint32_t dmask = m->dir_size - 1;
-  if (R) hipLaunchKernelGGL(k_rec_rank_fill, dim3(1024), dim3(256), 0, s, n, rk);
+  const uint32_t dmask = m->dir_size - 1, n = q.n;
+  if (q.end == RecEnd::Rank) hipLaunchKernelGGL(k_rec_rank_fill, dim3(1024), dim3(256), 0, s, n, q.rk);
   x.ctl.need(1); x.lds_list.need(n); x.big_list.need(n); x.big_off.need(n); x.tlg.need(n);
   HIP_OK(hipMemsetAsync(x.ctl.p, 0, sizeof(RecCtl), s));
-  hipLaunchKernelGGL(k_rec_bound<F>, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, d_off,
-                     d_items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, d_counts, f);
+  hipLaunchKernelGGL(REC_F(q, k_rec_bound), dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, q.off,
+                     q.items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, q.counts, q.f);
   HIP_OK(hipGetLastError());
   RecCtl c;
   HIP_OK(hipMemcpyAsync(&c, x.ctl.p, sizeof c, hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
-  if (F && c.bad) return -1;
-  if (c.n_lds && R)
-    hipLaunchKernelGGL(S ? k_rec_lds_rank_sim<F> : k_rec_lds_rank<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
-                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, rk, d_counts, f);
-  else if (c.n_lds && Q)
-    hipLaunchKernelGGL(S ? k_rec_lds_grouped_sim<F> : k_rec_lds_grouped<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
-                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f, gr);
-  else if (c.n_lds && D)
-    hipLaunchKernelGGL(S ? k_rec_lds_deep_sim<F> : k_rec_lds_deep<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir,
-                       dmask, m->arena.base, x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
-  else if (c.n_lds)
-    hipLaunchKernelGGL(S ? k_rec_lds_sim<F> : k_rec_lds<F>, dim3(std::min<uint32_t>(c.n_lds, 1u << 16)), dim3(REC_LDS_THREADS), 0, s, dir, dmask, m->arena.base,
-                       x.ctl.p, x.lds_list.p, x.tlg.p, d_off, d_items, k, d_ids, d_scores, d_counts, f);
+  if (q.filt && c.bad) return -1;
+  if (c.n_lds) rec_launch_lds(m, x, s, q, c.n_lds);
   HIP_OK(hipGetLastError());
   if (!c.n_big) return 0;
   const uint64_t ngroups = (c.total_slots + REC_GROUP_SLOTS - 1) / REC_GROUP_SLOTS;
@@ -233,7 +298,7 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
   const uint64_t nseg = cap / REC_SEG;
   const uint32_t np = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(c.max_len, REC_PLAN_MAX / c.n_big));
   x.gk.need(cap); x.gq.need(cap); x.gs.need(cap); x.owner.need(nseg); x.zpos.need(c.n_big);
-  if (!R && !Q && !D) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
+  if (q.end == RecEnd::TopK) { x.lk.need(nseg * 64); x.li.need(nseg * 64); }
   x.cnt.need((uint64_t)np * c.n_big); x.scan.need((uint64_t)np * c.n_big + 1);
   RecGl G{x.gk.p, x.gq.p, x.gs.p, x.owner.p, x.zpos.p, x.big_list.p, x.big_off.p, x.tlg.p, c.n_big, 0u, REC_GROUP_SLOTS};
   for (uint64_t g = 0; g < ngroups; g++) {
@@ -244,174 +309,118 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t*
     HIP_OK(hipMemsetAsync(x.gs.p, 0, ext * 8, s));
     HIP_OK(hipMemsetAsync(x.owner.p, 0xff, nseg * 4, s));
     HIP_OK(hipMemsetAsync(x.zpos.p, 0, (size_t)c.n_big * 4, s));
-    hipLaunchKernelGGL(k_rec_gl_init<F>, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, G, d_off, d_items, f);
+    hipLaunchKernelGGL(REC_F(q, k_rec_gl_init), dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(256), 0, s, G, q.off, q.items, q.f);
     HIP_OK(hipGetLastError());
     for (uint32_t p0 = 0; p0 < c.max_len; p0 += np) {
       const uint32_t nj = std::min<uint32_t>(np, c.max_len - p0);
       const uint64_t nt = (uint64_t)nj * c.n_big;
-      hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, G, dir, dmask, d_off, d_items, p0, nj, x.cnt.p);
+      hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, G, dir, dmask, q.off, q.items, p0, nj, x.cnt.p);
       HIP_OK(hipGetLastError());
       rec_scan(x, s, x.cnt.p, nt, x.scan.p);
       for (uint32_t j = 0; j < nj; j++)
-        hipLaunchKernelGGL(S ? k_rec_gl_scan_sim<F> : k_rec_gl_scan<F>, dim3(2048), dim3(256), 0, s, G, dir, dmask, m->arena.base, d_off,
-                           d_items, p0, j, x.scan.p, f);
+        hipLaunchKernelGGL(REC_FS(q, k_rec_gl_scan), dim3(2048), dim3(256), 0, s, G, dir, dmask, m->arena.base, q.off, q.items, p0, j, x.scan.p,
+                           q.f);
       HIP_OK(hipGetLastError());
     }
-    if (R) {
-      hipLaunchKernelGGL(k_rec_gl_rank, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, rk, d_counts);
-    } else if (Q) {
-      hipLaunchKernelGGL(k_rec_gl_grouped, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, gr, k, d_ids, d_scores,
-                         d_counts);
-    } else if (D) {
-      hipLaunchKernelGGL(k_rec_gl_deep, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, k, d_ids, d_scores, d_counts);
-    } else {
-      hipLaunchKernelGGL(k_rec_gl_topk, dim3((uint32_t)std::min<uint64_t>((nseg + 3) / 4, 16384)), dim3(256), 0, s, G, nseg, k, x.lk.p,
-                         x.li.p);
-      hipLaunchKernelGGL(k_rec_gl_merge, dim3(std::min<uint32_t>(c.n_big, 1u << 16)), dim3(REC_MERGE_THREADS), 0, s, G, k, x.lk.p, x.li.p,
-                         d_ids, d_scores, d_counts);
-    }
+    rec_launch_tail(x, s, q, G, nseg);
     HIP_OK(hipGetLastError());
   }
   return 0;
 }
 
-// what both flavours of the plain call refuse, and of the filtered call before anything else
-bool rec_k_ok(size_t n_sessions, uint32_t k) { return k != 0 && k <= 64 && n_sessions <= 0xffffffffull; }
-bool rec_filt_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n,
-                      uint32_t k) {
-  if (!rec_k_ok(n_sessions, k)) return false;
-  if (deny_n > (1ull << 32) || (!deny_bits && deny_n)) return false;
-  return (ex_offsets == nullptr) == (ex_items == nullptr);
-}
-bool rec_filt_any(const RecFilt& f) { return f.w || f.ex_off || f.deny_n; }
-// ... and the fill call on top of the sim call's
-bool rec_fill_args_ok(const void* fill_ids, uint64_t n_fill, const void* n_scored) {
-  return n_scored && n_fill < (1ull << 32) && (fill_ids || n_fill == 0);
-}
-// ... and the grouped call on top of the sim call's
-bool rec_group_args_ok(const void* group_of, uint64_t group_n, uint32_t cap) {
-  return cap != 0 && cap <= 64 && group_n <= (1ull << 32) && (group_of || group_n == 0);
-}
-// does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k:
-// both are the sim call, through its own launches
-bool rec_group_binds(const RecGroup& gr, uint32_t k) { return gr.n != 0 && gr.cap < k; }
-// what the deep call refuses in place of the sim call's k <= 64, and when its own ending runs: up to 64 results it IS the sim call
-bool rec_deep_k_ok(uint32_t k) { return k != 0 && k <= SMATRIX_DEEP_MAX; }
-bool rec_deep_binds(uint32_t k) { return k > 64; }
-static_assert(SMATRIX_DEEP_MAX == REC_DEEP_MAX, "the list of kernels/recommend.hpp holds SMATRIX_DEEP_MAX entries");
-// (the sim call refuses on top of them what sim_args_ok of smx_merge.inc refuses: shrink is a host scalar in both flavours)
-
-// the kernels' instances for what the call was given: <false, .> with no filter, <., true> with a measure; R: the rank ending;
-// gr: the grouped ending (never with R); deep: the deep ending (never with R or gr)
-template <bool R>
-int rec_dispatch(Matrix* m, RecScratch& x, hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k,
-                 uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecFilt& f, bool sim, const RecRank& rk,
-                 const RecGroup* gr = nullptr, bool deep = false) {
-  if constexpr (!R) {
-    if (deep && sim) return rec_filt_any(f) ? rec_run<true, true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
-                                            : rec_run<false, true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
-    if (deep) return rec_filt_any(f) ? rec_run<true, false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
-                                     : rec_run<false, false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
-    if (gr && sim) return rec_filt_any(f) ? rec_run<true, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
-                                          : rec_run<false, true, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr);
-    if (gr) return rec_filt_any(f) ? rec_run<true, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr)
-                                   : rec_run<false, false, false, true>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk, *gr);
-  }
-  if (sim) return rec_filt_any(f) ? rec_run<true, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
-                                  : rec_run<false, true, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
-  return rec_filt_any(f) ? rec_run<true, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk)
-                         : rec_run<false, false, R>(m, x, s, n, d_off, d_items, k, d_ids, d_scores, d_counts, f, rk);
-}
-
-// what smatrix_cf_recommend_fill adds to the sim call: the caller's list and where the scored counts go, all on the device
-struct RecFill {
-  const uint32_t* ids;
-  uint64_t n;
-  uint32_t* n_scored;
-};
 // behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session
-void rec_fill(hipStream_t s, uint32_t n, const uint64_t* d_off, const uint32_t* d_items, uint32_t k, const RecFill& fl, uint32_t* d_ids,
-              double* d_scores, uint32_t* d_counts, const RecFilt& f) {
-  hipLaunchKernelGGL(k_rec_fill, dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, n, d_off, d_items, k, fl.ids,
-                     (uint32_t)fl.n, d_ids, d_scores, d_counts, fl.n_scored, f);
+void rec_fill(hipStream_t s, const RecReq& q) {
+  hipLaunchKernelGGL(k_rec_fill, dim3(std::min<uint32_t>(blocks_for((uint64_t)q.n * 64), 16384)), dim3(256), 0, s, q.n, q.off, q.items, q.k,
+                     q.fl.ids, (uint32_t)q.fl.n, q.ids, q.scores, q.counts, q.fl.n_scored, q.f);
   HIP_OK(hipGetLastError());
 }
 
-// every _dev flavour behind its refusals: the scope around the driver.  R: the rank call (k, d_ids, d_scores: none); sim: score by
-// f.m, not by the cosine.  A bad weight is found on the device: -1 through the same finish.  fl: the fill call, its kernel behind
-// the driver's; gr: the grouped call, its ending in place of the top-k; deep: the deep call with k > 64, its ending in that place
-template <bool R>
-int rec_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const RecFilt& f, bool sim, uint32_t k,
-            uint32_t* d_ids, double* d_scores, uint32_t* d_counts, const RecRank& rk, void* hip_stream, const RecFill* fl = nullptr,
-            const RecGroup* gr = nullptr, bool deep = false) {
-  if (n_sessions == 0) return 0;
-  RecCall c(self, hip_stream);
-  const int rc = rec_dispatch<R>(c.m, c.x(), c.s, (uint32_t)n_sessions, d_offsets, d_items, k, d_ids, d_scores, d_counts, f, sim, rk, gr, deep);
-  if (fl && rc == 0) rec_fill(c.s, (uint32_t)n_sessions, d_offsets, d_items, k, *fl, d_ids, d_scores, d_counts, f);
+#undef REC_FS
+#undef REC_F
+
+// A host flavour's request on the device: what the request names is staged, and nothing else.  The rank call's answers are the
+// targets' [t_offsets[0], t_offsets[n]); the other endings' unused entries read 0, as cf_topk_batch's (n * k: 64-bit throughout);
+// the fill list goes through the stager as a list of lists that holds one list.
+RecReq rec_stage(RecCall& c, const RecReq& q) {
+  RecScratch& x = c.x();
+  const uint64_t n = q.n;
+  RecReq d = q;
+  const RecList ses = c.stage(n, q.off, q.items, x.h_off, x.h_items);
+  d.off = ses.off; d.items = ses.val;
+  d.f = c.stage_filter(n, q.off, q.f.w, q.f.ex_off, q.f.ex, q.f.deny, q.f.deny_n, q.f.m);
+  x.h_counts.need(n);
+  d.counts = x.h_counts.p;
+  if (q.end == RecEnd::Rank) {
+    const RecList t = c.stage(n, q.rk.t_off, q.rk.targets, x.h_toff, x.h_tg);
+    x.h_ranks.need(std::max<uint64_t>(t.count, 1)); x.h_scores.need(std::max<uint64_t>(t.count, 1));
+    d.rk = RecRank{t.off, t.val, x.h_ranks.p, x.h_scores.p};
+  } else {
+    x.h_ids.need(n * q.k); x.h_scores.need(n * q.k);
+    HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * q.k * 4, c.s));
+    HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * q.k * 8, c.s));
+    d.ids = x.h_ids.p; d.scores = x.h_scores.p;
+  }
+  if (q.end == RecEnd::Grouped) {
+    x.h_grp.need(q.gr.n);
+    HIP_OK(hipMemcpyAsync(x.h_grp.p, q.gr.of, q.gr.n * 4, hipMemcpyHostToDevice, c.s));
+    d.gr.of = x.h_grp.p;
+  }
+  if (q.fl.n_scored) {
+    const uint64_t one_list[2] = {0, q.fl.n};
+    const RecList l = c.stage(1, one_list, q.fl.ids, x.h_foff, x.h_fill);
+    x.h_nsc.need(n);
+    d.fl = RecFill{l.val, l.count, x.h_nsc.p};
+  }
+  return d;
+}
+
+// ... and its answers, from the staged request d back to the caller's q
+void rec_copy_back(RecCall& c, const RecReq& q, const RecReq& d) {
+  const uint64_t n = q.n;
+  HIP_OK(hipMemcpyAsync(q.counts, d.counts, n * 4, hipMemcpyDeviceToHost, c.s));
+  if (q.end == RecEnd::Rank) {
+    const uint64_t t0 = q.rk.t_off[0], count = q.rk.t_off[n] - t0;
+    if (count) HIP_OK(hipMemcpyAsync(q.rk.ranks + t0, d.rk.ranks, count * 4, hipMemcpyDeviceToHost, c.s));
+    if (count) HIP_OK(hipMemcpyAsync(q.rk.scores + t0, d.rk.scores, count * 8, hipMemcpyDeviceToHost, c.s));
+  } else {
+    HIP_OK(hipMemcpyAsync(q.ids, d.ids, n * q.k * 4, hipMemcpyDeviceToHost, c.s));
+    HIP_OK(hipMemcpyAsync(q.scores, d.scores, n * q.k * 8, hipMemcpyDeviceToHost, c.s));
+  }
+  if (q.fl.n_scored) HIP_OK(hipMemcpyAsync(q.fl.n_scored, d.fl.n_scored, n * 4, hipMemcpyDeviceToHost, c.s));
+}
+
+// Every session call behind its refusals.  No sessions: 0, and no scope.  A host flavour checks its weights before the device is
+// touched, so its driver result is 0; a _dev flavour's bad weight is found on the device: -1 through the same finish, and no fill.
+int rec_call(smatrix_t* self, const RecReq& q, bool host, void* hip_stream = nullptr) {
+  if (q.n == 0) return 0;
+  if (host && !rec_host_weights_ok(q.f.w, q.off, q.n)) return -1;
+  RecCall c(self, host, hip_stream);
+  const RecReq d = host ? rec_stage(c, q) : q;
+  const int rc = rec_run(c.m, c.x(), c.s, d);
+  if (d.fl.n_scored && rc == 0) rec_fill(c.s, d);
+  if (host) rec_copy_back(c, q, d);
   return c.finish(rc);
 }
 
-// the host flavours of the plain, the filtered and the sim call (the weights were checked here: the driver's result says nothing);
-// fl: the fill call, with the HOST's list and n_scored -- the list goes through the stager as a list of lists that holds one list;
-// gr: the grouped call, with the HOST's map, staged once; deep: the deep call with k > 64 (n * k: 64-bit throughout)
-int rec_filtered_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
-                      const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, uint32_t k,
-                      uint32_t* ids, double* scores, uint32_t* counts, bool sim, SimArgs f_m, const RecFill* fl = nullptr,
-                      const RecGroup* gr = nullptr, bool deep = false) {
-  if (n_sessions == 0) return 0;
-  const uint64_t n = n_sessions;
-  if (!rec_host_weights_ok(weights, offsets, n)) return -1;
-  RecCall c(self);
-  RecScratch& x = c.x();
-  const RecList q = c.stage(n, offsets, items, x.h_off, x.h_items);
-  const RecFilt f = c.stage_filter(n, offsets, weights, ex_offsets, ex_items, deny_bits, deny_n, f_m);
-  x.h_ids.need(n * k); x.h_scores.need(n * k); x.h_counts.need(n);
-  HIP_OK(hipMemsetAsync(x.h_ids.p, 0, n * k * 4, c.s));              // unused entries read 0, as cf_topk_batch's
-  HIP_OK(hipMemsetAsync(x.h_scores.p, 0, n * k * 8, c.s));
-  RecGroup d_gr{};
-  if (gr) {
-    x.h_grp.need(gr->n);
-    HIP_OK(hipMemcpyAsync(x.h_grp.p, gr->of, gr->n * 4, hipMemcpyHostToDevice, c.s));
-    d_gr = RecGroup{x.h_grp.p, gr->n, gr->cap};
-  }
-  rec_dispatch<false>(c.m, x, c.s, (uint32_t)n, q.off, q.val, k, x.h_ids.p, x.h_scores.p, x.h_counts.p, f, sim, RecRank{}, gr ? &d_gr : nullptr, deep);
-  if (fl) {
-    const uint64_t one_list[2] = {0, fl->n};
-    const RecList l = c.stage(1, one_list, fl->ids, x.h_foff, x.h_fill);
-    x.h_nsc.need(n);
-    rec_fill(c.s, (uint32_t)n, q.off, q.val, k, RecFill{l.val, l.count, x.h_nsc.p}, x.h_ids.p, x.h_scores.p, x.h_counts.p, f);
-    HIP_OK(hipMemcpyAsync(fl->n_scored, x.h_nsc.p, n * 4, hipMemcpyDeviceToHost, c.s));
-  }
-  HIP_OK(hipMemcpyAsync(counts, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, c.s));
-  HIP_OK(hipMemcpyAsync(ids, x.h_ids.p, n * k * 4, hipMemcpyDeviceToHost, c.s));
-  HIP_OK(hipMemcpyAsync(scores, x.h_scores.p, n * k * 8, hipMemcpyDeviceToHost, c.s));
-  return c.finish(0);
+// what every session call refuses, both flavours alike: a measure or a shrinkage that is none (sim_args_ok of smx_merge.inc: shrink is
+// a host scalar in both flavours), too many sessions, a deny bitmap or exclusion lists given by half
+bool rec_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n, int sim,
+                 double shrink) {
+  if (!sim_args_ok(sim, shrink) || n_sessions > 0xffffffffull) return false;
+  if (deny_n > (1ull << 32) || (!deny_bits && deny_n)) return false;
+  return (ex_offsets == nullptr) == (ex_items == nullptr);
 }
-
-// the rank call's: the same staging, and the target lists and the answers' [t_offsets[0], t_offsets[n]) beside it
-int rec_rank_host(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
-                  const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, bool sim, SimArgs f_m,
-                  const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores, uint32_t* n_candidates) {
-  if (n_sessions == 0) return 0;
-  const uint64_t n = n_sessions;
-  if (!rec_host_weights_ok(weights, offsets, n)) return -1;
-  RecCall c(self);
-  RecScratch& x = c.x();
-  const RecList q = c.stage(n, offsets, items, x.h_off, x.h_items), t = c.stage(n, t_offsets, targets, x.h_toff, x.h_tg);
-  const RecFilt f = c.stage_filter(n, offsets, weights, ex_offsets, ex_items, deny_bits, deny_n, f_m);
-  x.h_counts.need(n); x.h_ranks.need(std::max<uint64_t>(t.count, 1)); x.h_scores.need(std::max<uint64_t>(t.count, 1));
-  rec_dispatch<true>(c.m, x, c.s, (uint32_t)n, q.off, q.val, 0u, nullptr, nullptr, x.h_counts.p, f, sim,
-                     RecRank{t.off, t.val, x.h_ranks.p, x.h_scores.p});
-  HIP_OK(hipMemcpyAsync(n_candidates, x.h_counts.p, n * 4, hipMemcpyDeviceToHost, c.s));
-  if (t.count) HIP_OK(hipMemcpyAsync(ranks + t_offsets[0], x.h_ranks.p, t.count * 4, hipMemcpyDeviceToHost, c.s));
-  if (t.count) HIP_OK(hipMemcpyAsync(scores + t_offsets[0], x.h_scores.p, t.count * 8, hipMemcpyDeviceToHost, c.s));
-  return c.finish(0);
+// ... and what a call adds: the k of the top-k ending's 64 lanes, or the deep call's in its place
+bool rec_k_ok(uint32_t k) { return k != 0 && k <= 64; }
+bool rec_deep_k_ok(uint32_t k) { return k != 0 && k <= SMATRIX_DEEP_MAX; }
+static_assert(SMATRIX_DEEP_MAX == REC_DEEP_MAX, "the list of kernels/recommend.hpp holds SMATRIX_DEEP_MAX entries");
+// ... the fill call's list and n_scored
+bool rec_fill_args_ok(const void* fill_ids, uint64_t n_fill, const void* n_scored) {
+  return n_scored && n_fill < (1ull << 32) && (fill_ids || n_fill == 0);
 }
-
-// what both flavours of the rank call refuse before anything else (k: there is none)
-bool rec_rank_args_ok(size_t n_sessions, const void* ex_offsets, const void* ex_items, const void* deny_bits, uint64_t deny_n, int sim,
-                      double shrink, const void* t_offsets, const void* targets) {
-  return sim_args_ok(sim, shrink) && rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, 1u) && t_offsets && targets;
+// ... the grouped call's map and quota
+bool rec_group_args_ok(const void* group_of, uint64_t group_n, uint32_t cap) {
+  return cap != 0 && cap <= 64 && group_n <= (1ull << 32) && (group_of || group_n == 0);
 }
 
 void recommend_release(Matrix* m) {
@@ -429,50 +438,51 @@ extern "C" {
 
 int smatrix_cf_recommend_batch_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, uint32_t k,
                                    uint32_t* d_ids, double* d_scores, uint32_t* d_counts, void* hip_stream) {
-  if (!rec_k_ok(n_sessions, k)) return -1;
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items, RecFilt{}, false, k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
+  if (!rec_args_ok(n_sessions, nullptr, nullptr, nullptr, 0, SMATRIX_SIM_COSINE, 0.0) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, nullptr, nullptr, nullptr, nullptr, 0, SMATRIX_SIM_COSINE, 0.0,
+                                RecEnd::TopK, k, d_ids, d_scores, d_counts), false, hip_stream);
 }
 
 int smatrix_cf_recommend_batch(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, uint32_t k,
                                uint32_t* ids, double* scores, uint32_t* counts) {
-  if (!rec_k_ok(n_sessions, k)) return -1;
-  return rec_filtered_host(self, n_sessions, offsets, items, nullptr, nullptr, nullptr, nullptr, 0, k, ids, scores, counts, false, SimArgs{});
+  if (!rec_args_ok(n_sessions, nullptr, nullptr, nullptr, 0, SMATRIX_SIM_COSINE, 0.0) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, nullptr, nullptr, nullptr, nullptr, 0, SMATRIX_SIM_COSINE, 0.0,
+                                RecEnd::TopK, k, ids, scores, counts), true);
 }
 
 int smatrix_cf_recommend_filtered_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
                                       const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
                                       const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t k, uint32_t* d_ids, double* d_scores,
                                       uint32_t* d_counts, void* hip_stream) {
-  if (!rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items, RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{}}, false,
-                        k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SMATRIX_SIM_COSINE, 0.0) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SMATRIX_SIM_COSINE, 0.0,
+                                RecEnd::TopK, k, d_ids, d_scores, d_counts), false, hip_stream);
 }
 
 int smatrix_cf_recommend_filtered(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
                                   const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
                                   const uint32_t* deny_bits, uint64_t deny_n, uint32_t k, uint32_t* ids, double* scores,
                                   uint32_t* counts) {
-  if (!rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
-  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
-                           false, SimArgs{});
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, SMATRIX_SIM_COSINE, 0.0) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, SMATRIX_SIM_COSINE, 0.0,
+                                RecEnd::TopK, k, ids, scores, counts), true);
 }
 
 int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
                                  const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
                                  const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* d_ids,
                                  double* d_scores, uint32_t* d_counts, void* hip_stream) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
-                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
-                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream);
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::TopK, k, d_ids, d_scores, d_counts), false, hip_stream);
 }
 
 int smatrix_cf_recommend_sim(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                              const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
                              double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
-  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
-                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink});
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::TopK, k, ids, scores, counts), true);
 }
 
 int smatrix_cf_recommend_fill_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
@@ -480,23 +490,18 @@ int smatrix_cf_recommend_fill_dev(smatrix_t* self, size_t n_sessions, const uint
                                   const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_fill_ids, uint64_t n_fill, int sim,
                                   double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts, uint32_t* d_n_scored,
                                   void* hip_stream) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  if (!rec_fill_args_ok(d_fill_ids, n_fill, d_n_scored)) return -1;
-  const RecFill fl{d_fill_ids, n_fill, d_n_scored};
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
-                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
-                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, &fl);
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_fill_args_ok(d_fill_ids, n_fill, d_n_scored)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::TopK, k, d_ids, d_scores, d_counts, RecRank{}, RecGroup{}, RecFill{d_fill_ids, n_fill, d_n_scored}), false, hip_stream);
 }
 
 int smatrix_cf_recommend_fill(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                               const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n,
                               const uint32_t* fill_ids, uint64_t n_fill, int sim, double shrink, uint32_t k, uint32_t* ids, double* scores,
                               uint32_t* counts, uint32_t* n_scored) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
-  if (!rec_fill_args_ok(fill_ids, n_fill, n_scored)) return -1;
-  const RecFill fl{fill_ids, n_fill, n_scored};
-  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
-                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, &fl);
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_fill_args_ok(fill_ids, n_fill, n_scored)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::TopK, k, ids, scores, counts, RecRank{}, RecGroup{}, RecFill{fill_ids, n_fill, n_scored}), true);
 }
 
 int smatrix_cf_recommend_grouped_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
@@ -504,63 +509,53 @@ int smatrix_cf_recommend_grouped_dev(smatrix_t* self, size_t n_sessions, const u
                                      const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_group_of, uint64_t group_n, uint32_t cap,
                                      int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
                                      void* hip_stream) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, k)) return -1;
-  if (!rec_group_args_ok(d_group_of, group_n, cap)) return -1;
-  const RecGroup gr{d_group_of, group_n, cap};
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
-                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
-                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, nullptr,
-                        rec_group_binds(gr, k) ? &gr : nullptr);
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(d_group_of, group_n, cap)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, d_ids, d_scores, d_counts, RecRank{}, RecGroup{d_group_of, group_n, cap}), false, hip_stream);
 }
 
 int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                                  const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n,
                                  const uint32_t* group_of, uint64_t group_n, uint32_t cap, int sim, double shrink, uint32_t k, uint32_t* ids,
                                  double* scores, uint32_t* counts) {
-  if (!sim_args_ok(sim, shrink) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, k)) return -1;
-  if (!rec_group_args_ok(group_of, group_n, cap)) return -1;
-  const RecGroup gr{group_of, group_n, cap};
-  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
-                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, nullptr, rec_group_binds(gr, k) ? &gr : nullptr);
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(group_of, group_n, cap)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, ids, scores, counts, RecRank{}, RecGroup{group_of, group_n, cap}), true);
 }
 
 int smatrix_cf_recommend_deep_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
                                   const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
                                   const uint32_t* d_deny_bits, uint64_t deny_n, int sim, double shrink, uint32_t k, uint32_t* d_ids,
                                   double* d_scores, uint32_t* d_counts, void* hip_stream) {
-  if (!sim_args_ok(sim, shrink) || !rec_deep_k_ok(k) || !rec_filt_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, 1u)) return -1;
-  return rec_dev<false>(self, n_sessions, d_offsets, d_items,
-                        RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
-                        !sim_is_plain_cosine(sim, shrink), k, d_ids, d_scores, d_counts, RecRank{}, hip_stream, nullptr, nullptr,
-                        rec_deep_binds(k));
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_deep_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::Deep, k, d_ids, d_scores, d_counts), false, hip_stream);
 }
 
 int smatrix_cf_recommend_deep(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                               const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
                               double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts) {
-  if (!sim_args_ok(sim, shrink) || !rec_deep_k_ok(k) || !rec_filt_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, 1u)) return -1;
-  return rec_filtered_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, k, ids, scores, counts,
-                           !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, nullptr, nullptr, rec_deep_binds(k));
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_deep_k_ok(k)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::Deep, k, ids, scores, counts), true);
 }
 
 int smatrix_cf_rank_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items, const double* d_weights,
                         const uint64_t* d_ex_offsets, const uint32_t* d_ex_items, const uint32_t* d_deny_bits, uint64_t deny_n, int sim,
                         double shrink, const uint64_t* d_t_offsets, const uint32_t* d_targets, uint32_t* d_ranks, double* d_scores,
                         uint32_t* d_n_candidates, void* hip_stream) {
-  if (!rec_rank_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink, d_t_offsets, d_targets)) return -1;
-  return rec_dev<true>(self, n_sessions, d_offsets, d_items,
-                       RecFilt{d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, SimArgs{sim, shrink}},
-                       !sim_is_plain_cosine(sim, shrink), 0u, nullptr, nullptr, d_n_candidates,
-                       RecRank{d_t_offsets, d_targets, d_ranks, d_scores}, hip_stream);
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !d_t_offsets || !d_targets) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::Rank, 0u, nullptr, nullptr, d_n_candidates, RecRank{d_t_offsets, d_targets, d_ranks, d_scores}), false, hip_stream);
 }
 
 int smatrix_cf_rank(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
                     const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim,
                     double shrink, const uint64_t* t_offsets, const uint32_t* targets, uint32_t* ranks, double* scores,
                     uint32_t* n_candidates) {
-  if (!rec_rank_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink, t_offsets, targets)) return -1;
-  return rec_rank_host(self, n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n,
-                       !sim_is_plain_cosine(sim, shrink), SimArgs{sim, shrink}, t_offsets, targets, ranks, scores, n_candidates);
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !t_offsets || !targets) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::Rank, 0u, nullptr, nullptr, n_candidates, RecRank{t_offsets, targets, ranks, scores}), true);
 }
 
 }  // extern "C"

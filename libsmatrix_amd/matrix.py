@@ -289,6 +289,16 @@ def _p(a, to=_lib.u32p):
 _DP = C.POINTER(C.c_double)
 
 
+def _topk_outputs(n, k):
+    """the outputs of a top-k-shaped session call: -> (ids[n,k], scores[n,k] float64, counts[n]), zeros"""
+    return np.zeros((n, k), dtype=np.uint32), np.zeros((n, k), dtype=np.float64), np.zeros(n, dtype=np.uint32)
+
+
+def _stream_ptr(stream):
+    """a _dev method's stream as the C call takes it: a torch.cuda.Stream's handle, or a hipStream_t as int or None as they are"""
+    return getattr(stream, "cuda_stream", stream)
+
+
 class SparseMatrix:
     def __init__(self, filename=None):
         """filename None = in-memory (SparseMatrix.java:70-77); else open-or-create the file."""
@@ -440,9 +450,7 @@ class SparseMatrix:
         _check_k(k)
         offsets, items = _sessions(sessions)
         n = len(sessions)
-        ids = np.zeros((n, k), dtype=np.uint32)
-        scores = np.zeros((n, k), dtype=np.float64)
-        counts = np.zeros(n, dtype=np.uint32)
+        ids, scores, counts = _topk_outputs(n, k)
         if n and self._lib.smatrix_cf_recommend_batch(self._h, n, offsets.ctypes.data_as(_lib.u64p), _p(items), k,
                                                       ids.ctypes.data_as(_lib.u32p),
                                                       scores.ctypes.data_as(C.POINTER(C.c_double)), _p(counts)) != 0:
@@ -453,8 +461,7 @@ class SparseMatrix:
         """the same on device arrays (raw pointers): offsets uint64[n+1], items uint32, ids uint32[n*k], scores float64[n*k],
         counts uint32[n].  stream: a torch.cuda.Stream or a hipStream_t as int (None: the legacy default stream, synchronised)"""
         _check_k(k)
-        sp = getattr(stream, "cuda_stream", stream)
-        if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+        if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
 
     def _cf_front(self, sessions, weights, exclude, deny, sim, shrink, targets=None):
@@ -486,9 +493,7 @@ class SparseMatrix:
         shrink is a finite number >= 0.  The defaults make the call above"""
         _check_k(k)
         n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids = np.zeros((n, k), dtype=np.uint32)
-        scores = np.zeros((n, k), dtype=np.float64)
-        counts = np.zeros(n, dtype=np.uint32)
+        ids, scores, counts = _topk_outputs(n, k)
         back = (k, _p(ids), _p(scores, _DP), _p(counts))
         if measure == (0, 0.0):
             if n and self._lib.smatrix_cf_recommend_filtered(*sess, *filt, *back) != 0:
@@ -503,9 +508,8 @@ class SparseMatrix:
         float64 per item, ex_off uint64[n+1], ex_items uint32, deny uint32[(deny_n + 31) / 32].  A bad weight is found on the
         device: ValueError, the outputs' contents unspecified"""
         _check_k(k)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_filtered_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                       deny_n, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+                                                       deny_n, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_filtered_dev: bad k, n, weights, exclusion lists or deny bitmap")
 
     def cf_recommend_sim_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, k,
@@ -513,9 +517,8 @@ class SparseMatrix:
         """cf_recommend_filtered_dev with cf_recommend_filtered's sim and shrink (smatrix_cf_recommend_sim_dev)"""
         _check_k(k)
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_sim_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                  deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+                                                  deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_sim_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
 
     def cf_popular(self, n, deny=None, min_total=1):
@@ -536,8 +539,8 @@ class SparseMatrix:
         ids uint32[n], totals uint32[n], n_found uint32[1].  No read-back: nothing is returned, the entries beyond n_found are
         left as they were"""
         _popular_args(n, min_total)
-        sp = getattr(stream, "cuda_stream", stream)
-        if self._lib.smatrix_cf_popular_dev(self._h, deny_ptr, deny_n, int(min_total), int(n), ids_ptr, totals_ptr, n_found_ptr, sp) != 0:
+        if self._lib.smatrix_cf_popular_dev(self._h, deny_ptr, deny_n, int(min_total), int(n), ids_ptr, totals_ptr, n_found_ptr,
+                                            _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_popular_dev: bad n, deny bitmap or outputs")
 
     def cf_recommend_filled(self, sessions, k, fill, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
@@ -549,9 +552,7 @@ class SparseMatrix:
         _check_k(k)
         fill = _fill_ids(fill)
         n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids = np.zeros((n, k), dtype=np.uint32)
-        scores = np.zeros((n, k), dtype=np.float64)
-        counts = np.zeros(n, dtype=np.uint32)
+        ids, scores, counts = _topk_outputs(n, k)
         n_scored = np.zeros(n, dtype=np.uint32)
         if n and self._lib.smatrix_cf_recommend_fill(*sess, *filt, _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids),
                                                      _p(scores, _DP), _p(counts), _p(n_scored)) != 0:
@@ -564,9 +565,9 @@ class SparseMatrix:
         (None with n_fill 0: no list), n_scored uint32[n]"""
         _check_k(k)
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                   fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, sp) != 0:
+                                                   fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr,
+                                                   _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, fill, sim or shrink")
 
     def cf_recommend_grouped(self, sessions, k, group_of, cap, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
@@ -580,9 +581,7 @@ class SparseMatrix:
         _check_cap(cap)
         groups = _group_map(group_of)
         n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids = np.zeros((n, k), dtype=np.uint32)
-        scores = np.zeros((n, k), dtype=np.float64)
-        counts = np.zeros(n, dtype=np.uint32)
+        ids, scores, counts = _topk_outputs(n, k)
         if n and self._lib.smatrix_cf_recommend_grouped(*sess, *filt, _p(groups), 0 if groups is None else int(groups.size), int(cap), *measure,
                                                         k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
             raise ValueError("smatrix_cf_recommend_grouped: bad k, n_sessions, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
@@ -595,9 +594,9 @@ class SparseMatrix:
         _check_k(k)
         _check_cap(cap)
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_grouped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                      group_ptr, group_n, int(cap), code, h, k, ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+                                                      group_ptr, group_n, int(cap), code, h, k, ids_ptr, scores_ptr, cnt_ptr,
+                                                      _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_grouped_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
 
     def cf_recommend_deep(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
@@ -608,9 +607,7 @@ class SparseMatrix:
         _check_deep_k(k)
         k = int(k)
         n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids = np.zeros((n, k), dtype=np.uint32)
-        scores = np.zeros((n, k), dtype=np.float64)
-        counts = np.zeros(n, dtype=np.uint32)
+        ids, scores, counts = _topk_outputs(n, k)
         if n and self._lib.smatrix_cf_recommend_deep(*sess, *filt, *measure, k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
             raise ValueError("smatrix_cf_recommend_deep: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
         return ids, scores, counts
@@ -621,9 +618,8 @@ class SparseMatrix:
         ids uint32[n*k], scores float64[n*k]"""
         _check_deep_k(k)
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_recommend_deep_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                   deny_n, code, h, int(k), ids_ptr, scores_ptr, cnt_ptr, sp) != 0:
+                                                   deny_n, code, h, int(k), ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_deep_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
 
     def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
@@ -646,9 +642,8 @@ class SparseMatrix:
         """the same on device arrays (raw pointers, None for a filter that is not given): cf_recommend_sim_dev's inputs, and
         t_off uint64[n+1], targets uint32, ranks uint32 and scores float64 parallel to targets, ncand uint32[n]"""
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_rank_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, code, h,
-                                         t_off_ptr, targets_ptr, ranks_ptr, scores_ptr, ncand_ptr, sp) != 0:
+                                         t_off_ptr, targets_ptr, ranks_ptr, scores_ptr, ncand_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_rank_dev: bad n, weights, exclusion lists, deny bitmap, sim, shrink or targets")
 
     def cf_explain(self, sessions, targets, weights=None, sim="cosine", shrink=0.0):
@@ -675,9 +670,8 @@ class SparseMatrix:
         total = e_off[n], terms float64[total], cc uint32[total].  A bad weight is found on the device: ValueError, the outputs'
         contents unspecified"""
         code, h = _sim(sim), _shrink(shrink)
-        sp = getattr(stream, "cuda_stream", stream)
         if self._lib.smatrix_cf_explain_dev(self._h, n, off_ptr, items_ptr, weights_ptr, code, h, t_off_ptr, targets_ptr, e_off_ptr, total,
-                                            terms_ptr, cc_ptr, sp) != 0:
+                                            terms_ptr, cc_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_explain_dev: bad n, weights, sim, shrink, targets or entry offsets")
 
     def cf_recommend_explained(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
