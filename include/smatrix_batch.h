@@ -215,8 +215,7 @@ int smatrix_cf_recommend_sim_dev(smatrix_t* self, size_t n_sessions, const uint6
  * global tier is ended by one workgroup over its whole table (as smatrix_cf_rank's).  The host flavour stages group_of once per call.
  * Returns -1 for smatrix_cf_recommend_sim's refusals, word for word, and for cap == 0, cap > 64, group_n > 2^32 and group_of NULL
  * with group_n != 0 (before the device is touched, outputs as they were, both flavours).  0 otherwise.
- * Not here: a cap per group (an array of quotas), a back-fill that knows the quotas (smatrix_cf_recommend_fill under caps), and the
- * sharded matrix. */
+ * Not here: a cap per group (an array of quotas) and the sharded matrix. */
 #define SMATRIX_GROUP_NONE 0xFFFFFFFFu
 int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
                                  const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
@@ -397,6 +396,50 @@ int smatrix_cf_recommend_fill_dev(smatrix_t* self, size_t n_sessions, const uint
                                   const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_fill_ids, uint64_t n_fill,
                                   int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
                                   uint32_t* d_n_scored, void* hip_stream);
+
+/* k results AND at most `cap` of one group: smatrix_cf_recommend_fill under caps.  smatrix_cf_recommend_grouped, then the free places
+ * of a short result filled from the caller's list under the session's own filters and under the same quotas -- ten results, never
+ * more than two of one brand, never fewer than ten.  Everything not said here is smatrix_cf_recommend_grouped's and
+ * smatrix_cf_recommend_fill's contract, word for word: sessions, candidates, scores, filters, group_of / group_n / cap, fill_ids /
+ * n_fill, tiers, locks, the mirror, streams, scratch, k <= 64.
+ *   scored     exactly smatrix_cf_recommend_grouped with the same arguments: n_scored[s] is its counts[s], and the entries
+ *              [s*k, s*k + n_scored[s]) of ids / scores are its bytes, through its own launches in both tiers.
+ *   fill       when n_scored[s] < k, fill_ids[0 .. n_fill) is walked in list order and id f is appended with score +0.0 iff it
+ *              passes every test of smatrix_cf_recommend_fill (f != 0, not an item of the session at any position, not on its
+ *              exclusion list, not denied, not in the result already, scored or filled) AND f is ungrouped (f >= group_n or
+ *              group_of[f] == SMATRIX_GROUP_NONE) or fewer than cap entries of the session's result so far, scored and filled
+ *              together, have the group group_of[f].  An id refused by its quota does not end the walk, and a repeat of it is
+ *              refused again; a repeat of an id that was taken is in the result already and consumes nothing.  The walk stops at
+ *              k entries or at the list's end; counts[s] = n_scored[s] + the ids appended, which may still be < k.
+ *   candidates left behind: under quotas n_scored[s] < k no longer means that the session's candidates are used up -- the ones the
+ *              quota refused are still there.  Each of them belongs to a group that is full, and a full group stays full, so the
+ *              fill's quota refuses it as well when the list offers it: a filled id is still never one of the session's candidates.
+ *   no quota   a map that cannot bind (group_of NULL with group_n == 0, or cap >= k) makes the call smatrix_cf_recommend_fill: its
+ *              bytes in all four outputs through its launches.
+ *   empty list fill_ids NULL with n_fill == 0: smatrix_cf_recommend_grouped's bytes and n_scored = counts.
+ *   unused     entries beyond counts[s]: the host flavour zero-fills them, _dev leaves them.
+ * Deterministic: the same contents and input give the same bytes.
+ * Cost beyond the grouped call's: the fill call's one launch, a wave per session; a session with counts[s] == k ends after one load.
+ * A session that fills gathers one group per scored result once and one per list id that passed the fill's own tests, and decides
+ * the quotas of 64 list ids at a time from two counts (the result's entries of the id's group, the step's earlier ids of it): 64
+ * more compares per id walked than the fill call's.  Ids of full groups are walked past, 64 a step: a list dominated by one brand
+ * costs its length / 64 steps.  The host flavour stages group_of and fill_ids once per call.
+ * Returns -1 for smatrix_cf_recommend_grouped's refusals and smatrix_cf_recommend_fill's, word for word (both flavours before the
+ * device is touched, outputs as they were; a bad weight as in the fill call: the host flavour before the device is touched, _dev on
+ * the device, and nothing is filled behind it).  0 otherwise.
+ * Not here: a cap per group, k > 64 (smatrix_cf_recommend_deep has neither list nor quotas), a fill list per session, and the sharded
+ * matrix. */
+int smatrix_cf_recommend_grouped_fill(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                      const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                                      const uint32_t* deny_bits, uint64_t deny_n, const uint32_t* group_of, uint64_t group_n,
+                                      uint32_t cap, const uint32_t* fill_ids, uint64_t n_fill, int sim, double shrink, uint32_t k,
+                                      uint32_t* ids, double* scores, uint32_t* counts, uint32_t* n_scored);
+int smatrix_cf_recommend_grouped_fill_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                          const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                          const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_group_of,
+                                          uint64_t group_n, uint32_t cap, const uint32_t* d_fill_ids, uint64_t n_fill, int sim,
+                                          double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
+                                          uint32_t* d_n_scored, void* hip_stream);
 
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,

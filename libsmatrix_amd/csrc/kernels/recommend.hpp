@@ -30,6 +30,8 @@
 // rec_deep_table: up to REC_DEEP_MAX results, by a radix select of the k-th best key and a workgroup sort of what is at or above it.
 // smatrix_cf_recommend_fill (k_rec_fill, at the end of this file): the sim call's launches as they are, and one more behind them that
 // fills the free places of a short result from the caller's list under the session's own filters.
+// smatrix_cf_recommend_grouped_fill (k_rec_fill_grouped, behind k_rec_fill): the grouped call's launches as they are, and the fill under
+// the same quotas: the groups of the results live in lanes beside the ids, and a step's quota is decided by counts, without a walk.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -1088,6 +1090,75 @@ __global__ __launch_bounds__(256) void k_rec_fill(uint32_t n, const uint64_t* __
       for (uint32_t j = 0; j < 64; j++) {
         const uint32_t o = (uint32_t)__shfl((int)fid, (int)j);
         if ((uint32_t)__shfl((int)to, (int)j) == lane) mine = o;
+      }
+      const uint32_t room = k - have, found = (uint32_t)__popcll(m);
+      have += found < room ? found : room;
+    }
+    if (lane == 0) counts[s] = have;
+  }
+}
+
+// ---- smatrix_cf_recommend_grouped_fill: the same behind the grouped ending, under its quotas ---------------------------------
+// k_rec_fill with the groups beside the ids: `mg` is the group of the result in `mine` (REC_GROUP_NONE in a free place), one gather
+// from gr.of per scored result at the start.  A step first finishes `ok` exactly as k_rec_fill does -- so of the lanes that hold
+// one id only the lowest is still ok, and a repeated id counts once --, then gathers the group of every lane still ok, g.  Lane i is a
+// SURVIVOR iff it is ungrouped or (the lanes j < have with mg_j == g) + (the ok lanes j < i with g_j == g) < cap: rec_group_table's
+// argument.  An ok lane of group g below i that is no survivor found the group full, and a full group stays full, so lane i finds it
+// full as well; and when every ok lane of group g below i survived, the sum IS the count of the serial walk.  Both counts come from
+// one more 64-step shuffle loop, over mg and g.  The survivors are numbered by mbcnt behind `have` and cut at the room left (the
+// session is full behind a cut: the lanes it drops decide nothing any more), and the id AND its group go to the lane that owns the
+// new place.  A step whose lanes are all refused -- 64 ids of full groups -- takes nothing and the walk goes on.
+__global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                          uint32_t k, const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids,
+                                                          double* scores, uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f,
+                                                          RecGroup gr) {
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t s = wave; s < n; s += nwaves) {                     // (wave-uniform throughout: the shuffles need every lane)
+    uint32_t have = counts[s];
+    if (lane == 0) n_scored[s] = have;
+    if (have >= k || n_fill == 0) continue;
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    const uint64_t e0 = f.ex_off ? f.ex_off[s] : 0ull, E = f.ex_off ? f.ex_off[s + 1] - e0 : 0ull;
+    uint32_t mine = lane < have ? ids[(uint64_t)s * k + lane] : 0u;
+    uint32_t mg = lane < have && mine < gr.n ? gr.of[mine] : REC_GROUP_NONE;
+    for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
+      const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
+      bool ok = fid != 0 && !rec_denied(f, fid);
+      if (!__any(ok)) continue;
+      for (uint64_t c0 = 0; c0 < L; c0 += 64) {
+        const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint64_t c0 = 0; c0 < E; c0 += 64) {
+        const uint32_t e = c0 + lane < E ? f.ex[e0 + c0 + lane] : 0u;
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);   // (every lane shuffles)
+        ok &= r != fid;                                             // in the result, scored or filled by an earlier step
+        ok &= !(j < lane && o == fid);                              // a lane below holds the same id
+      }
+      if (!__any(ok)) continue;
+      const uint32_t g = ok && fid < gr.n ? gr.of[fid] : REC_GROUP_NONE;   // (a lane that is not ok is in no group: it counts for nobody)
+      uint32_t same = 0;
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t r = (uint32_t)__shfl((int)mg, (int)j), o = (uint32_t)__shfl((int)g, (int)j);
+        same += (r == g ? 1u : 0u) + (j < lane && o == g ? 1u : 0u);
+      }
+      const bool sv = ok && (g == REC_GROUP_NONE || same < gr.cap);
+      const uint64_t m = __ballot(sv);
+      if (m == 0) continue;
+      const uint32_t place = have + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const bool take = sv && place < k;                            // the room left is the cut
+      if (take) {
+        ids[(uint64_t)s * k + place] = fid;
+        scores[(uint64_t)s * k + place] = 0.0;
+      }
+      const uint32_t to = take ? place : 0xffffffffu;               // ... and the lane that owns the place holds id and group from here on
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j), og = (uint32_t)__shfl((int)g, (int)j);
+        if ((uint32_t)__shfl((int)to, (int)j) == lane) { mine = o; mg = og; }
       }
       const uint32_t room = k - have, found = (uint32_t)__popcll(m);
       have += found < room ? found : room;

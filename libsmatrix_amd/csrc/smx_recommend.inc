@@ -1,6 +1,7 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
 // smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_fill / _dev,
-// smatrix_cf_recommend_grouped / _dev, smatrix_cf_recommend_deep / _dev and smatrix_cf_rank / _dev), host side.
+// smatrix_cf_recommend_grouped / _dev, smatrix_cf_recommend_grouped_fill / _dev, smatrix_cf_recommend_deep / _dev and
+// smatrix_cf_rank / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -37,6 +38,9 @@
 // quota that cannot bind (cap >= k), and the deep call with k <= 64 ARE the sim call, through the same launches.
 // The fill call (smatrix_cf_recommend_fill / _dev) is the sim call with ONE launch behind the driver's, rec_fill: k_rec_fill reads
 // the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).
+// The grouped fill call (smatrix_cf_recommend_grouped_fill / _dev) is the grouped call with that launch behind it: a request with a
+// RecGroup AND a RecFill.  Where the map binds, rec_fill launches k_rec_fill_grouped, the fill under the same quotas; where it cannot,
+// rec_req has made the request the fill call's, k_rec_fill included.
 
 namespace {
 
@@ -220,7 +224,8 @@ struct RecReq {
   uint32_t* counts;                           // [n]; Rank: the candidate counts
   RecRank rk;                                 // Rank: the target lists and their answers
   RecGroup gr;                                // Grouped: the map and the quota
-  RecFill fl;                                 // the fill call (fl.n_scored is given): k_rec_fill behind the driver's launches
+  RecFill fl;                                 // the fill calls (fl.n_scored is given): k_rec_fill behind the driver's launches, behind the
+                                              // Grouped ending k_rec_fill_grouped
 };
 
 // does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k
@@ -328,10 +333,15 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
   return 0;
 }
 
-// behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session
+// behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session -- behind the grouped ending
+// k_rec_fill_grouped, the same under the request's quotas
 void rec_fill(hipStream_t s, const RecReq& q) {
-  hipLaunchKernelGGL(k_rec_fill, dim3(std::min<uint32_t>(blocks_for((uint64_t)q.n * 64), 16384)), dim3(256), 0, s, q.n, q.off, q.items, q.k,
-                     q.fl.ids, (uint32_t)q.fl.n, q.ids, q.scores, q.counts, q.fl.n_scored, q.f);
+  auto launch = [&](auto kernel, auto... quotas) {
+    hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(blocks_for((uint64_t)q.n * 64), 16384)), dim3(256), 0, s, q.n, q.off, q.items, q.k,
+                       q.fl.ids, (uint32_t)q.fl.n, q.ids, q.scores, q.counts, q.fl.n_scored, q.f, quotas...);
+  };
+  if (q.end == RecEnd::Grouped) launch(k_rec_fill_grouped, q.gr);
+  else launch(k_rec_fill);
   HIP_OK(hipGetLastError());
 }
 
@@ -521,6 +531,30 @@ int smatrix_cf_recommend_grouped(smatrix_t* self, size_t n_sessions, const uint6
   if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(group_of, group_n, cap)) return -1;
   return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
                                 RecEnd::Grouped, k, ids, scores, counts, RecRank{}, RecGroup{group_of, group_n, cap}), true);
+}
+
+int smatrix_cf_recommend_grouped_fill_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                          const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                          const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_group_of, uint64_t group_n,
+                                          uint32_t cap, const uint32_t* d_fill_ids, uint64_t n_fill, int sim, double shrink, uint32_t k,
+                                          uint32_t* d_ids, double* d_scores, uint32_t* d_counts, uint32_t* d_n_scored, void* hip_stream) {
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(d_group_of, group_n, cap) ||
+      !rec_fill_args_ok(d_fill_ids, n_fill, d_n_scored)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, d_ids, d_scores, d_counts, RecRank{}, RecGroup{d_group_of, group_n, cap},
+                                RecFill{d_fill_ids, n_fill, d_n_scored}), false, hip_stream);
+}
+
+int smatrix_cf_recommend_grouped_fill(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                      const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits,
+                                      uint64_t deny_n, const uint32_t* group_of, uint64_t group_n, uint32_t cap, const uint32_t* fill_ids,
+                                      uint64_t n_fill, int sim, double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts,
+                                      uint32_t* n_scored) {
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(group_of, group_n, cap) ||
+      !rec_fill_args_ok(fill_ids, n_fill, n_scored)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, ids, scores, counts, RecRank{}, RecGroup{group_of, group_n, cap},
+                                RecFill{fill_ids, n_fill, n_scored}), true);
 }
 
 int smatrix_cf_recommend_deep_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,

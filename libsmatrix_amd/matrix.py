@@ -599,6 +599,40 @@ class SparseMatrix:
                                                       _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_grouped_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
 
+    def cf_recommend_grouped_filled(self, sessions, k, group_of, cap, fill, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_grouped, then the free places of a short result filled from `fill` under the same quotas (include/
+        smatrix_batch.h smatrix_cf_recommend_grouped_fill): k results, and still at most `cap` of one group.  group_of and cap are
+        cf_recommend_grouped's, fill is cf_recommend_filled's; an id of the list is appended with score 0.0 iff cf_recommend_filled
+        would append it and it is ungrouped or fewer than cap entries of the result so far, scored and filled, share its group.
+        -> (ids[n,k], scores[n,k] float64, counts[n], n_scored[n]) as cf_recommend_filled: the first n_scored[s] entries of session
+        s are cf_recommend_grouped's"""
+        _check_k(k)
+        _check_cap(cap)
+        groups = _group_map(group_of)
+        fill = _fill_ids(fill)
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        ids, scores, counts = _topk_outputs(n, k)
+        n_scored = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_grouped_fill(*sess, *filt, _p(groups), 0 if groups is None else int(groups.size), int(cap),
+                                                             _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids),
+                                                             _p(scores, _DP), _p(counts), _p(n_scored)) != 0:
+            raise ValueError("smatrix_cf_recommend_grouped_fill: bad k, n_sessions, weights, exclusion lists, deny bitmap, group map, cap, fill, "
+                             "sim or shrink")
+        return ids, scores, counts, n_scored
+
+    def cf_recommend_grouped_fill_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n,
+                                      cap, fill_ptr, n_fill, sim, shrink, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given): cf_recommend_grouped_dev's, and fill uint32[n_fill]
+        (None with n_fill 0: no list), n_scored uint32[n]"""
+        _check_k(k)
+        _check_cap(cap)
+        code, h = _sim(sim), _shrink(shrink)
+        if self._lib.smatrix_cf_recommend_grouped_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
+                                                           group_ptr, group_n, int(cap), fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr,
+                                                           cnt_ptr, n_scored_ptr, _stream_ptr(stream)) != 0:
+            raise ValueError("smatrix_cf_recommend_grouped_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, fill, sim "
+                             "or shrink")
+
     def cf_recommend_deep(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_filtered with up to DEEP_MAX = 1024 results per session (include/smatrix_batch.h smatrix_cf_recommend_deep):
         the candidates for a second-stage ranker, for re-ranking on the caller's side, for recall@k beyond 64.  Every argument is
