@@ -31,6 +31,11 @@ uint32_t smatrix_shard_of(uint32_t x, uint32_t nshards);
  *   d_place : the few hot rows placed one by one: `place_slots` (a power of two <= 1024, or 0 for none)
  *             entries {x, owner + 1} in device memory, open addressing, slot of x =
  *             smatrix_place_slot(x, place_slots), linear probing, owner + 1 == 0 marks an empty slot.
+ *             PRECONDITIONS of a table handed straight to the partition calls (the kernels cannot check a device
+ *             table): it keeps at least one empty slot -- the look-up of an id that is not in a FULL table never
+ *             ends -- and every owner it names is below nshards -- a larger one indexes past the kernels' per-shard
+ *             counters.  smatrix_shard_set_placement checks both for its host table and keeps half of the slots empty:
+ *             at most 512 rows are placed one by one.
  * A row's owner is its d_place entry if it has one, else the range its hash falls in. */
 uint32_t smatrix_shard_mix(uint32_t x);
 uint32_t smatrix_place_slot(uint32_t x, uint32_t place_slots);
@@ -54,7 +59,8 @@ int smatrix_partition_packed_dev(size_t n, const uint32_t* d_x, const uint32_t* 
                                  uint32_t* d_packed, const uint32_t* d_place, uint32_t place_slots,
                                  const uint32_t* d_cuts, void* hip_stream);
 
-/* records of `width` words -> separate x/y[/v] arrays (the form the op kernels consume) */
+/* records of `width` words -> separate x/y[/v] arrays (the form the op kernels consume).  This call and
+ * smatrix_gather_dev return 0, or -1 before anything is launched: width not 2 or 3, n >= 2^32. */
 int smatrix_unpack_dev(size_t n, uint32_t width, const uint32_t* d_packed, uint32_t* d_x, uint32_t* d_y,
                        uint32_t* d_v, void* hip_stream);
 
@@ -103,7 +109,9 @@ const char* smatrix_shard_transport(smatrix_shard_t* sh);       /* "self" (one r
 const char* smatrix_shard_rccl_library(int* version);
 
 /* a placement chosen by the caller instead (see PLACEMENT above), identical on every rank, before the first batch:
- * cuts: nranks-1 host words or NULL; place_pairs: place_slots x {x, owner+1} host words (open addressing as above) */
+ * cuts: nranks-1 host words or NULL; place_pairs: place_slots x {x, owner+1} host words (open addressing as above).
+ * Returns 0, or -1 and leaves the placement in force as it was: place_slots no power of two or above 1024, an owner
+ * >= nranks, more than 512 non-empty pairs. */
 int smatrix_shard_set_placement(smatrix_shard_t* sh, const uint32_t* cuts, const uint32_t* place_pairs, uint32_t place_slots);
 /* the placement in force: cuts_out (nranks-1 words, *n_cuts = 0 for equal ranges), up to cap_rows {x, owner} pairs of
  * the rows placed one by one (*n_rows = how many there are).  Returns 1 once the placement is settled, else 0. */

@@ -3212,7 +3212,7 @@ size_t smatrix_displaced_rows(smatrix_t* self, uint32_t rank, uint32_t nshards, 
 
 int smatrix_unpack_dev(size_t n, uint32_t width, const uint32_t* d_packed, uint32_t* d_x, uint32_t* d_y,
                        uint32_t* d_v, void* hip_stream) {
-  if (width != 2 && width != 3) return -1;
+  if ((width != 2 && width != 3) || n >= (1ull << 32)) return -1;   // (the kernel counts in 32 bits, like the partition)
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_unpack, dim3(blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
                      (uint32_t)n, width, d_packed, d_x, d_y, d_v);
@@ -3222,6 +3222,7 @@ int smatrix_unpack_dev(size_t n, uint32_t width, const uint32_t* d_packed, uint3
 
 int smatrix_gather_dev(size_t n, const uint32_t* d_src, const uint32_t* d_perm, uint32_t* d_out,
                        void* hip_stream) {
+  if (n >= (1ull << 32)) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_gather, dim3(blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(hip_stream),
                      (uint32_t)n, d_src, d_perm, d_out);

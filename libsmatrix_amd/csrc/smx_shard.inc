@@ -1049,6 +1049,9 @@ int smatrix_shard_set_placement(smatrix_shard_t* sh, const uint32_t* cuts, const
       if (place_pairs[2 * i + 1] > (uint32_t)sh->nranks) return -1;
       pl.place.push_back({place_pairs[2 * i], place_pairs[2 * i + 1] - 1u});
     }
+  // (the device table is sized at twice the rows, shard_upload_placement: more than half of PLACE_MAX_SLOTS do not fit.
+  //  Refused here, before the plan is replaced: the handle keeps the placement it had)
+  if (pl.place.size() > PLACE_MAX_SLOTS / 2) return -1;
   std::sort(pl.place.begin(), pl.place.end());
   sh->plan = pl;
   sh->placed = true;
