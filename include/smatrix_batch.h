@@ -441,6 +441,58 @@ int smatrix_cf_recommend_grouped_fill_dev(smatrix_t* self, size_t n_sessions, co
                                           double shrink, uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts,
                                           uint32_t* d_n_scored, void* hip_stream);
 
+/* Recommendations from these categories only: smatrix_cf_recommend_grouped_fill with a scope per session -- a category page,
+ * "accessories for this item", "more from this seller", a user's muted categories.  A scope is a per-session deny decided by the
+ * candidate's group, applied on the GPU where a candidate is made, before the cut at k: a session whose best 64 candidates hold two
+ * pairs of shoes still gets its 10 results for the shoe page.  The five arguments behind deny_n are new; everything not said here is
+ * smatrix_cf_recommend_grouped_fill's contract, word for word, its special cases included (a map group_of that cannot bind makes it
+ * the fill call, an empty fill list the grouped call, both together the sim call): one call covers a scope with any of filters,
+ * measure, quotas and back-fill.  k <= 64.
+ *   scope_of   one uint32 per id 0 .. scope_n - 1, scope_n <= 2^32: a second map, independent of group_of -- category here, brand
+ *              there; the same array may be passed twice.  g(b) = scope_of[b] for b < scope_n, else SMATRIX_GROUP_NONE.
+ *   sc_offsets, sc_groups   session s's scope list is sc_groups[sc_offsets[s] .. sc_offsets[s+1]): at most SMATRIX_SCOPE_MAX entries,
+ *              repeats allowed, an entry SMATRIX_GROUP_NONE matches nothing.  sc_offsets has n_sessions + 1 entries and need not
+ *              start at 0 (host flavour).
+ *   listed(s, b)   g(b) != SMATRIX_GROUP_NONE and g(b) occurs in session s's list.
+ *   unscoped   a session with an empty list is unscoped in both modes: every id is allowed.  One batch mixes scoped and unscoped
+ *              sessions.
+ *   scope_mode SMATRIX_SCOPE_ONLY: otherwise b is allowed iff listed(s, b); an ungrouped id is never given to a scoped session.
+ *              SMATRIX_SCOPE_EXCEPT: otherwise b is allowed iff !listed(s, b); ungrouped ids pass.  One mode for the call.
+ *   not allowed   an id that is not allowed is treated exactly as an id on the session's exclusion list: it is no candidate, consumes
+ *              no quota, does not count in n_scored or counts, and the fill walks past it without ending the walk.  As an ITEM of
+ *              the session it stays an item: its row is scanned and its weight counts.
+ *   equivalence   the four outputs are the bytes of smatrix_cf_recommend_grouped_fill with the same arguments, when that call is given
+ *              session s's exclusion list extended by every id that is not allowed for s.
+ *   no scope   sc_offsets NULL (then sc_groups and scope_of must be NULL and scope_n 0) writes smatrix_cf_recommend_grouped_fill's
+ *              bytes through that call's own launches.
+ *   unused     entries beyond counts[s]: the host flavour zero-fills them, _dev leaves them.
+ * Deterministic: the same contents and input give the same bytes; nothing depends on slot order, lane order or the tier.
+ * Cost beyond the grouped fill call's: per DISTINCT candidate key of a scoped session (not per term) one 4-byte gather from scope_of
+ * and at most SMATRIX_SCOPE_MAX compares against the session's list, read from global memory at an address the wave shares; per fill
+ * step of 64 list ids one gather and 64 compares per id.  An unscoped session of a scoped batch pays one length test per key.  The
+ * host flavour stages scope_of once per call and the lists as it stages the exclusion lists.
+ * Returns -1 for smatrix_cf_recommend_grouped_fill's refusals, word for word, and for an unknown scope_mode, scope_n > 2^32, scope_of
+ * NULL with scope_n != 0, exactly one of sc_offsets / sc_groups NULL, a map given without lists (all before the device is touched,
+ * outputs as they were, both flavours), and for a list longer than SMATRIX_SCOPE_MAX, found as a bad weight is found: the host
+ * flavour walks sc_offsets before the device is touched, _dev finds it on the device, leaves the outputs unspecified, and nothing
+ * is filled behind it.  0 otherwise.
+ * Not here: k > 64, smatrix_cf_rank / smatrix_cf_explain under a scope, a mode per session, and the sharded matrix. */
+#define SMATRIX_SCOPE_MAX 64
+enum { SMATRIX_SCOPE_ONLY = 0, SMATRIX_SCOPE_EXCEPT = 1 };
+int smatrix_cf_recommend_scoped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items,
+                                const double* weights, const uint64_t* ex_offsets, const uint32_t* ex_items,
+                                const uint32_t* deny_bits, uint64_t deny_n, const uint32_t* scope_of, uint64_t scope_n,
+                                const uint64_t* sc_offsets, const uint32_t* sc_groups, int scope_mode, const uint32_t* group_of,
+                                uint64_t group_n, uint32_t cap, const uint32_t* fill_ids, uint64_t n_fill, int sim, double shrink,
+                                uint32_t k, uint32_t* ids, double* scores, uint32_t* counts, uint32_t* n_scored);
+int smatrix_cf_recommend_scoped_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                    const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                    const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_scope_of, uint64_t scope_n,
+                                    const uint64_t* d_sc_offsets, const uint32_t* d_sc_groups, int scope_mode,
+                                    const uint32_t* d_group_of, uint64_t group_n, uint32_t cap, const uint32_t* d_fill_ids,
+                                    uint64_t n_fill, int sim, double shrink, uint32_t k, uint32_t* d_ids, double* d_scores,
+                                    uint32_t* d_counts, uint32_t* d_n_scored, void* hip_stream);
+
 /* CF-recommender write path, on the device (examples/cf_recommender.c:36-47 import_preference_set): session s is
  * ids[offsets[s] .. offsets[s+1]); for every position n of a session  incr(ids[n], 0, 1)  and, for every OTHER position i,
  * incr(ids[n], ids[i], 1) -- L*L ops for a session of L ids, generated on the GPU and applied as incr batches (the

@@ -8,6 +8,6 @@
 The compute path is lib/smatrix.so (HIP); importing works without a GPU, opening a
 matrix does not.
 """
-from .matrix import (DEEP_MAX, GROUP_NONE, IMPORT_FORWARD, IMPORT_NO_SELF, OP_DECR, OP_GET, OP_INCR, OP_SET, POPULAR_MAX, RANK_NONE, SparseMatrix,  # noqa: F401
-                     device_available, explain_table, rank_metrics)
+from .matrix import (DEEP_MAX, GROUP_NONE, IMPORT_FORWARD, IMPORT_NO_SELF, OP_DECR, OP_GET, OP_INCR, OP_SET, POPULAR_MAX, RANK_NONE, SCOPE_EXCEPT, SCOPE_MAX,  # noqa: F401
+                     SCOPE_ONLY, SparseMatrix, device_available, explain_table, rank_metrics)
 from .stream import Stream  # noqa: F401

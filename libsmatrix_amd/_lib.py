@@ -100,6 +100,11 @@ def load():
                                                         C.POINTER(C.c_double), u32p, u32p]),
         "smatrix_cf_recommend_grouped_fill_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, V, C.c_uint64, C.c_uint32, V, C.c_uint64,
                                                             C.c_int, C.c_double, C.c_uint32, V, V, V, V, V]),
+        "smatrix_cf_recommend_scoped": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64, u32p, C.c_uint64,
+                                                  u64p, u32p, C.c_int, u32p, C.c_uint64, C.c_uint32, u32p, C.c_uint64, C.c_int, C.c_double,
+                                                  C.c_uint32, u32p, C.POINTER(C.c_double), u32p, u32p]),
+        "smatrix_cf_recommend_scoped_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, V, C.c_uint64, V, V, C.c_int, V, C.c_uint64,
+                                                      C.c_uint32, V, C.c_uint64, C.c_int, C.c_double, C.c_uint32, V, V, V, V, V]),
         "smatrix_cf_recommend_deep": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64,
                                                 C.c_int, C.c_double, C.c_uint32, u32p, C.POINTER(C.c_double), u32p]),
         "smatrix_cf_recommend_deep_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, C.c_int, C.c_double, C.c_uint32, V, V, V, V]),

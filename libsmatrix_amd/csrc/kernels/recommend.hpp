@@ -32,6 +32,11 @@
 // fills the free places of a short result from the caller's list under the session's own filters.
 // smatrix_cf_recommend_grouped_fill (k_rec_fill_grouped, behind k_rec_fill): the grouped call's launches as they are, and the fill under
 // the same quotas: the groups of the results live in lanes beside the ids, and a step's quota is decided by counts, without a walk.
+// smatrix_cf_recommend_scoped (RecScope; k_rec_lds_scoped, k_rec_lds_grouped_scoped and k_rec_gl_scan_scoped, over the same bodies
+// with C set; k_rec_scope_bound and k_rec_fill_scoped at the end of this file): the grouped fill call with a per-session deny decided
+// by the id's group in a second map.  The test stands where rec_denied stands, on a claimed key of either tier -- once per distinct
+// key of a session --, and an out-of-scope key gets sqrt = -1 like a denied one, so the endings and the tables know nothing of it;
+// k_rec_fill_scoped tests the list's ids the same way.  The existing instances have C == false and keep their code.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -208,6 +213,36 @@ struct RecGroup {
   uint64_t n;
   uint32_t cap;
 };
+// what smatrix_cf_recommend_scoped adds: a per-session deny decided by the id's group in a map of its own, of[b] for b < n, else
+// REC_GROUP_NONE.  Session s lists gr[off[s] .. off[s+1]), at most REC_SCOPE_MAX groups; with an empty list it is unscoped.  An id is
+// LISTED when its group is not REC_GROUP_NONE and occurs in the list; a scoped session is given the listed ids alone (except == 0)
+// or every id but the listed ones (except != 0).
+constexpr uint32_t REC_SCOPE_MAX = 64;        // SMATRIX_SCOPE_MAX: the fill kernels hold a list one entry per lane
+struct RecScope {
+  const uint32_t* of;
+  uint64_t n;
+  const uint64_t* off;
+  const uint32_t* gr;
+  uint32_t except;
+};
+// session s's list as {first entry, length}.  A longer list than REC_SCOPE_MAX is a refusal (k_rec_scope_bound sets RecCtl::bad
+// and nothing runs behind it); the cut only keeps every reader inside 64 entries
+__device__ __forceinline__ uint32_t rec_scope_len(const RecScope& sc, uint32_t s, uint64_t* l0) {
+  *l0 = sc.off[s];
+  const uint64_t nl = sc.off[s + 1] - *l0;
+  return (uint32_t)(nl < REC_SCOPE_MAX ? nl : REC_SCOPE_MAX);
+}
+// is key b kept from a session whose list is gr[l0 .. l0 + nl)?  One gather from the map, then nl compares against words at
+// addresses the whole wave shares (the list lies in global memory: the LDS tier has no word to spare)
+__device__ __forceinline__ bool rec_out_of_scope(const RecScope& sc, uint64_t l0, uint32_t nl, uint32_t b) {
+  if (nl == 0) return false;
+  const uint32_t g = b < sc.n ? sc.of[b] : REC_GROUP_NONE;
+  bool listed = false;
+  if (g != REC_GROUP_NONE)
+    for (uint32_t j = 0; j < nl; j++) listed |= sc.gr[l0 + j] == g;
+  return listed == (sc.except != 0);
+}
+
 // the LDS words the grouped ending needs beside the table: NW lists of 64 {key, id, group}, the <= 64 groups a round fills, and
 // {the round's verdict, the key and the id of the last candidate it looked at}
 constexpr uint32_t REC_GRP_DONE = 0xffffffffu;
@@ -569,13 +604,15 @@ __global__ __launch_bounds__(256) void k_rec_bound(DirSlot* dir, uint32_t dmask,
 // (the body of k_rec_lds<F> and of k_rec_lds_sim<F>; S: the score is f.m's, not the cosine's; R: smatrix_cf_rank's ending in place
 // of the top-k, k_rec_lds_rank<F> and k_rec_lds_rank_sim<F>: scores and counts are then the targets' and the candidate counts;
 // G: smatrix_cf_recommend_grouped's ending, rec_group_table, k_rec_lds_grouped<F> and k_rec_lds_grouped_sim<F>;
-// D: smatrix_cf_recommend_deep's ending, rec_deep_table, k_rec_lds_deep<F> and k_rec_lds_deep_sim<F>)
-template <bool F, bool S, bool R, bool G = false, bool D = false>
+// D: smatrix_cf_recommend_deep's ending, rec_deep_table, k_rec_lds_deep<F> and k_rec_lds_deep_sim<F>;
+// C: smatrix_cf_recommend_scoped's test on a claimed key, k_rec_lds_scoped and k_rec_lds_grouped_scoped)
+template <bool F, bool S, bool R, bool G = false, bool D = false, bool C = false>
 __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
                                         const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
                                         const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
                                         uint32_t* __restrict__ ids, double* __restrict__ scores, uint32_t* __restrict__ counts,
-                                        const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{}) {
+                                        const RecFilt& f, const RecRank& rk, const RecGroup& gr = RecGroup{},
+                                        const RecScope& sc = RecScope{}) {
   __shared__ uint32_t s_key[REC_LDS_SLOTS];
   __shared__ double s_sq[REC_LDS_SLOTS];
   __shared__ double s_sum[REC_LDS_SLOTS];
@@ -588,6 +625,8 @@ __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* a
     const uint32_t s = lds_list[q];
     const uint32_t tsize = 1u << tlg[s], mask = tsize - 1;    // (<= REC_LDS_SLOTS here)
     const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    uint64_t l0 = 0;                                                // the session's scope list (uniform; read where a key is claimed)
+    const uint32_t nl = C ? rec_scope_len(sc, s, &l0) : 0u;
     for (uint32_t i = tid; i < tsize; i += REC_LDS_THREADS) { s_key[i] = 0; s_sq[i] = 0.0; s_sum[i] = 0.0; }
     __syncthreads();
     for (uint32_t i = tid; i < L; i += REC_LDS_THREADS) {          // the session's items: excluded, first positions
@@ -632,13 +671,14 @@ __device__ __forceinline__ void rec_lds(DirSlot* dir, uint32_t dmask, uint8_t* a
         double sqb;
         if (claimed) {
           if (F && rec_denied(f, b)) { s_sq[h] = -1.0; continue; }  // a denied key: excluded from here on
+          if (C && rec_out_of_scope(sc, l0, nl, b)) { s_sq[h] = -1.0; continue; }   // ... and a key out of the session's scope
           sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
           s_sq[h] = sqb;
         } else {
           sqb = s_sq[h];
-          if (sqb < 0.0) continue;                                  // an item of the session, an excluded or a denied key
-          // claimed by another lane of this row (a twice-held key).  If that lane is about to deny the key, this term is added
-          // to a sum nobody reads: the selection below takes s_sq > 0 after the barrier
+          if (sqb < 0.0) continue;                                  // an item of the session, an excluded, a denied or an out-of-scope key
+          // claimed by another lane of this row (a twice-held key).  If that lane is about to deny the key, or to find it out of
+          // scope, this term is added to a sum nobody reads: the selection below takes s_sq > 0 after the barrier
           if (sqb == 0.0) sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
         }
         double term = rec_term<S>(cell_val(c), sa, sqb, f.m);
@@ -754,6 +794,26 @@ __global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_grouped_sim(DirSlot
   rec_lds<F, true, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{}, gr);
 }
 
+// smatrix_cf_recommend_scoped's instances: the filtered _sim bodies of the top-k and of the grouped ending with the scope test where a
+// key is claimed (plain cosine goes through sim_score too: sqrt(A) * sqrt(B) + 0.0 is the plain term's denominator, bit for bit)
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_scoped(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                    const uint32_t* __restrict__ lds_list, const uint8_t* __restrict__ tlg,
+                                                                    const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                                    uint32_t k, uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                    uint32_t* __restrict__ counts, RecFilt f, RecScope sc) {
+  rec_lds<true, true, false, false, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{},
+                                                 RecGroup{}, sc);
+}
+__global__ __launch_bounds__(REC_LDS_THREADS) void k_rec_lds_grouped_scoped(DirSlot* dir, uint32_t dmask, uint8_t* arena, const RecCtl* ctl,
+                                                                            const uint32_t* __restrict__ lds_list,
+                                                                            const uint8_t* __restrict__ tlg, const uint64_t* __restrict__ off,
+                                                                            const uint32_t* __restrict__ items, uint32_t k,
+                                                                            uint32_t* __restrict__ ids, double* __restrict__ scores,
+                                                                            uint32_t* __restrict__ counts, RecFilt f, RecGroup gr, RecScope sc) {
+  rec_lds<true, true, false, true, false, true>(dir, dmask, arena, ctl, lds_list, tlg, off, items, k, ids, scores, counts, f, RecRank{}, gr,
+                                                sc);
+}
+
 // smatrix_cf_recommend_deep's instances (k > 64): the same fill, rec_deep_table at the end
 static_assert(rec_deep_words() * 4 <= REC_LDS_SLOTS * 8, "the list, the bins and the control words share s_sq");
 template <bool F>
@@ -855,11 +915,12 @@ __global__ __launch_bounds__(256) void k_rec_gl_plan(RecGl R, DirSlot* dir, uint
 }
 
 // position p = p0 + j: a wave per chunk task; scan[j * n_big + idx] = the first task of session idx (scan of k_rec_gl_plan's counts)
-// (the body of k_rec_gl_scan<F> and of k_rec_gl_scan_sim<F>, as rec_lds)
-template <bool F, bool S>
+// (the body of k_rec_gl_scan<F>, of k_rec_gl_scan_sim<F> and, with C, of k_rec_gl_scan_scoped, as rec_lds)
+template <bool F, bool S, bool C = false>
 __device__ __forceinline__ void rec_gl_scan(const RecGl& R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
                                             const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
-                                            uint32_t j, const uint64_t* __restrict__ scan, const RecFilt& f) {
+                                            uint32_t j, const uint64_t* __restrict__ scan, const RecFilt& f,
+                                            const RecScope& scope = RecScope{}) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
   const uint64_t* sc = scan + (uint64_t)j * R.n_big;
@@ -873,6 +934,8 @@ __device__ __forceinline__ void rec_gl_scan(const RecGl& R, DirSlot* dir, uint32
     const uint32_t s = R.big_list[idx];
     const uint32_t mask = (uint32_t)((1ull << R.tlg[s]) - 1u);   // (tables of 2^32 slots: mask 2^32 - 1)
     const uint32_t a = items[off[s] + p0 + j];
+    uint64_t l0 = 0;                                                // the session's scope list (uniform per wave)
+    const uint32_t nl = C ? rec_scope_len(scope, s, &l0) : 0u;
     uint4 sn;
     dir_find(dir, dmask, a, &sn);                                   // (there: the plan gave it chunks)
     const double sa = rec_row_total<S>(dir, dmask, arena, a, f.m);
@@ -897,13 +960,14 @@ __device__ __forceinline__ void rec_gl_scan(const RecGl& R, DirSlot* dir, uint32
       double sqb;
       if (claimed) {
         if (F && rec_denied(f, b)) { sq[h] = -1.0; continue; }
+        if (C && rec_out_of_scope(scope, l0, nl, b)) { sq[h] = -1.0; continue; }
         sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);
         sq[h] = sqb;
       } else {
         sqb = __hip_atomic_load(&sq[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (sqb < 0.0) continue;
-        if (sqb == 0.0) sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);   // (a denied key's claimer may be between its claim and its
-      }                                                               // store: as in k_rec_lds, k_rec_gl_topk reads gq > 0 later)
+        if (sqb == 0.0) sqb = rec_col_total<S>(dir, dmask, arena, b, f.m);   // (the claimer of a denied or out-of-scope key may be between
+      }                                                               // its claim and its store: as in k_rec_lds, the endings read gq > 0 later)
       double term = rec_term<S>(cell_val(cv[u]), sa, sqb, f.m);
       if (F) term = __dmul_rn(wa, term);
       unsafeAtomicAdd(&sum[h], term);
@@ -922,6 +986,12 @@ __global__ __launch_bounds__(256) void k_rec_gl_scan_sim(RecGl R, DirSlot* dir, 
                                                          const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t p0,
                                                          uint32_t j, const uint64_t* __restrict__ scan, RecFilt f) {
   rec_gl_scan<F, true>(R, dir, dmask, arena, off, items, p0, j, scan, f);
+}
+__global__ __launch_bounds__(256) void k_rec_gl_scan_scoped(RecGl R, DirSlot* dir, uint32_t dmask, uint8_t* arena,
+                                                            const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                            uint32_t p0, uint32_t j, const uint64_t* __restrict__ scan, RecFilt f,
+                                                            RecScope sc) {
+  rec_gl_scan<true, true, true>(R, dir, dmask, arena, off, items, p0, j, scan, f, sc);
 }
 
 // a wave per REC_SEG-slot segment of the group's tables: its 64 best -> lk / li (64 entries per segment, best first)
@@ -1125,6 +1195,89 @@ __global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint
     for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
       const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
       bool ok = fid != 0 && !rec_denied(f, fid);
+      if (!__any(ok)) continue;
+      for (uint64_t c0 = 0; c0 < L; c0 += 64) {
+        const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint64_t c0 = 0; c0 < E; c0 += 64) {
+        const uint32_t e = c0 + lane < E ? f.ex[e0 + c0 + lane] : 0u;
+        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
+      }
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);   // (every lane shuffles)
+        ok &= r != fid;                                             // in the result, scored or filled by an earlier step
+        ok &= !(j < lane && o == fid);                              // a lane below holds the same id
+      }
+      if (!__any(ok)) continue;
+      const uint32_t g = ok && fid < gr.n ? gr.of[fid] : REC_GROUP_NONE;   // (a lane that is not ok is in no group: it counts for nobody)
+      uint32_t same = 0;
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t r = (uint32_t)__shfl((int)mg, (int)j), o = (uint32_t)__shfl((int)g, (int)j);
+        same += (r == g ? 1u : 0u) + (j < lane && o == g ? 1u : 0u);
+      }
+      const bool sv = ok && (g == REC_GROUP_NONE || same < gr.cap);
+      const uint64_t m = __ballot(sv);
+      if (m == 0) continue;
+      const uint32_t place = have + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      const bool take = sv && place < k;                            // the room left is the cut
+      if (take) {
+        ids[(uint64_t)s * k + place] = fid;
+        scores[(uint64_t)s * k + place] = 0.0;
+      }
+      const uint32_t to = take ? place : 0xffffffffu;               // ... and the lane that owns the place holds id and group from here on
+      for (uint32_t j = 0; j < 64; j++) {
+        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j), og = (uint32_t)__shfl((int)g, (int)j);
+        if ((uint32_t)__shfl((int)to, (int)j) == lane) { mine = o; mg = og; }
+      }
+      const uint32_t room = k - have, found = (uint32_t)__popcll(m);
+      have += found < room ? found : room;
+    }
+    if (lane == 0) counts[s] = have;
+  }
+}
+
+// ---- smatrix_cf_recommend_scoped: the lists measured, and the fill under a scope -----------------------------------------------
+// beside k_rec_bound, before the driver's one read-back: a scope list longer than REC_SCOPE_MAX is RecCtl::bad, as a bad weight is
+__global__ __launch_bounds__(256) void k_rec_scope_bound(uint32_t n, RecScope sc, RecCtl* ctl) {
+  for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x)
+    if (sc.off[s + 1] - sc.off[s] > REC_SCOPE_MAX) ctl->bad = 1u;
+}
+
+// k_rec_fill_grouped with the scope test: an id out of the session's scope is an excluded id.  The wave holds the session's scope
+// list one entry per lane, `sl` -- hence REC_SCOPE_MAX = 64 --, REC_GROUP_NONE in the lanes beyond its end, and tests a step's 64 ids
+// with one more 64-step shuffle loop, every lane shuffling: lane i's id is LISTED iff its group in sc.of is not REC_GROUP_NONE and
+// some lane's `sl` equals it.  The test is a function of the id alone, like every test before the quotas, and stands first, so a step
+// whose ids are all out of scope ends at the first __any.  An unscoped session (an empty list) skips it: nl is the wave's.
+// It is also the scoped fill WITHOUT quotas: under a RecGroup of no ids every lane is ungrouped, every ok lane a survivor, and the
+// kernel writes k_rec_fill's bytes.  Written out beside the two fill kernels, which keep their code.
+__global__ __launch_bounds__(256) void k_rec_fill_scoped(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                         uint32_t k, const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids,
+                                                         double* scores, uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f,
+                                                         RecGroup gr, RecScope sc) {
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t s = wave; s < n; s += nwaves) {                     // (wave-uniform throughout: the shuffles need every lane)
+    uint32_t have = counts[s];
+    if (lane == 0) n_scored[s] = have;
+    if (have >= k || n_fill == 0) continue;
+    const uint64_t b0 = off[s], L = off[s + 1] - b0;
+    const uint64_t e0 = f.ex_off ? f.ex_off[s] : 0ull, E = f.ex_off ? f.ex_off[s + 1] - e0 : 0ull;
+    uint32_t mine = lane < have ? ids[(uint64_t)s * k + lane] : 0u;
+    uint32_t mg = lane < have && mine < gr.n ? gr.of[mine] : REC_GROUP_NONE;
+    uint64_t l0;
+    const uint32_t nl = rec_scope_len(sc, s, &l0);
+    const uint32_t sl = lane < nl ? sc.gr[l0 + lane] : REC_GROUP_NONE;
+    for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
+      const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
+      bool ok = fid != 0 && !rec_denied(f, fid);
+      if (nl != 0) {
+        const uint32_t sg = ok && fid < sc.n ? sc.of[fid] : REC_GROUP_NONE;
+        bool listed = false;
+        for (uint32_t j = 0; j < 64; j++) listed |= (uint32_t)__shfl((int)sl, (int)j) == sg;   // (every lane shuffles)
+        listed &= sg != REC_GROUP_NONE;                             // (an ungrouped id is listed nowhere: REC_GROUP_NONE matches nothing)
+        ok &= listed == (sc.except == 0);
+      }
       if (!__any(ok)) continue;
       for (uint64_t c0 = 0; c0 < L; c0 += 64) {
         const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)

@@ -1,7 +1,7 @@
 // smx_recommend.inc -- session recommendations (include/smatrix_batch.h smatrix_cf_recommend_batch / _dev,
 // smatrix_cf_recommend_filtered / _dev, smatrix_cf_recommend_sim / _dev, smatrix_cf_recommend_fill / _dev,
-// smatrix_cf_recommend_grouped / _dev, smatrix_cf_recommend_grouped_fill / _dev, smatrix_cf_recommend_deep / _dev and
-// smatrix_cf_rank / _dev), host side.
+// smatrix_cf_recommend_grouped / _dev, smatrix_cf_recommend_grouped_fill / _dev, smatrix_cf_recommend_scoped / _dev,
+// smatrix_cf_recommend_deep / _dev and smatrix_cf_rank / _dev), host side.
 // Included by smx_runtime.hip inside the translation unit, after smx_export.inc (uses Matrix, DevBuf, HIP_OK, and the export's
 // u32 -> u64 scan kernels); the device code is kernels/recommend.hpp.
 //
@@ -41,6 +41,10 @@
 // The grouped fill call (smatrix_cf_recommend_grouped_fill / _dev) is the grouped call with that launch behind it: a request with a
 // RecGroup AND a RecFill.  Where the map binds, rec_fill launches k_rec_fill_grouped, the fill under the same quotas; where it cannot,
 // rec_req has made the request the fill call's, k_rec_fill included.
+// The scoped call (smatrix_cf_recommend_scoped / _dev) is the grouped fill call with a RecScope.  With lists given, the kernels that
+// decide what a candidate is -- the LDS tier's, k_rec_gl_scan and the fill's -- run as their _scoped instances (REC_SC), which exist
+// over the filtered _sim bodies alone, and k_rec_scope_bound measures the lists beside k_rec_bound, before the read-back; every other
+// launch is the grouped fill call's.  Without lists rec_req leaves the request unscoped: the grouped fill call, launch for launch.
 
 namespace {
 
@@ -70,6 +74,8 @@ struct RecScratch {
   DevBuf<uint64_t> h_foff;                           // ... and the fill call's: the staged list (one list: two offsets), n_scored
   DevBuf<uint32_t> h_fill, h_nsc;
   DevBuf<uint32_t> h_grp;                            // ... and the grouped call's: the group of every id
+  DevBuf<uint32_t> h_scp, h_scgr;                    // ... and the scoped call's: its own map, the sessions' scope lists
+  DevBuf<uint64_t> h_scoff;
   DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
   DevBuf<unsigned long long> p_keys, p_out;          // directory slot, the n keys collected (ids: h_ids, totals: h_counts, n: h_nsc)
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
@@ -78,7 +84,8 @@ struct RecScratch {
   void for_each_buf(Fn f) {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
-    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(h_grp); f(p_ctl); f(p_keys); f(p_out);
+    f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(h_grp); f(h_scp); f(h_scgr); f(h_scoff);
+    f(p_ctl); f(p_keys); f(p_out);
   }
 };
 
@@ -226,6 +233,8 @@ struct RecReq {
   RecGroup gr;                                // Grouped: the map and the quota
   RecFill fl;                                 // the fill calls (fl.n_scored is given): k_rec_fill behind the driver's launches, behind the
                                               // Grouped ending k_rec_fill_grouped
+  RecScope sc;                                // the scoped call: the map, the sessions' lists and the mode
+  bool scoped;                                // lists were given: the _scoped instances (and then filt and sim are set)
 };
 
 // does the map change anything?  Without ids in it nobody is grouped, and a quota of k or more refuses nobody before the cut at k
@@ -237,17 +246,22 @@ bool rec_group_binds(const RecGroup& gr, uint32_t k) { return gr.n != 0 && gr.ca
 // The one RecFilt literal is here too: NULL / 0 for what was not given; the calls without a measure pass SMATRIX_SIM_COSINE and 0.0.
 RecReq rec_req(size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights, const uint64_t* ex_offsets,
                const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n, int sim, double shrink, RecEnd end, uint32_t k, uint32_t* ids,
-               double* scores, uint32_t* counts, const RecRank& rk = RecRank{}, const RecGroup& gr = RecGroup{}, const RecFill& fl = RecFill{}) {
+               double* scores, uint32_t* counts, const RecRank& rk = RecRank{}, const RecGroup& gr = RecGroup{}, const RecFill& fl = RecFill{},
+               const RecScope& sc = RecScope{}) {
   const RecFilt f{weights, ex_offsets, ex_items, deny_bits, deny_n, SimArgs{sim, shrink}};
   if (end == RecEnd::Grouped && !rec_group_binds(gr, k)) end = RecEnd::TopK;
   if (end == RecEnd::Deep && k <= 64) end = RecEnd::TopK;                 // up to 64 results the top-k ending holds them
-  return RecReq{(uint32_t)n_sessions, offsets, items, f, f.w || f.ex_off || f.deny_n, !sim_is_plain_cosine(sim, shrink), end, k, ids, scores,
-                counts, rk, end == RecEnd::Grouped ? gr : RecGroup{}, fl};
+  const bool scoped = sc.off != nullptr;                                  // no lists: not scoped (the entry point has refused a map without)
+  return RecReq{(uint32_t)n_sessions, offsets, items, f, scoped || f.w || f.ex_off || f.deny_n, scoped || !sim_is_plain_cosine(sim, shrink), end, k,
+                ids, scores, counts, rk, end == RecEnd::Grouped ? gr : RecGroup{}, fl, scoped ? sc : RecScope{}, scoped};
 }
 
 // a kernel template's instance for request q: k<true> with a filter, k<false> without; and of k / k_sim the second for a measure
 #define REC_F(q, k) ((q).filt ? k<true> : k<false>)
 #define REC_FS(q, k) ((q).sim ? REC_F(q, k##_sim) : REC_F(q, k))
+// launch(kernel, args...) for request q, or launch(kernel_scoped, args..., q.sc) for a scoped one
+#define REC_SC(q, launch, kernel, scoped_kernel, ...) \
+  do { if ((q).scoped) launch(scoped_kernel, __VA_ARGS__, (q).sc); else launch(kernel, __VA_ARGS__); } while (0)
 
 // the LDS tier, one workgroup per session of lds_list: the ending's kernel stands for k_rec_lds, behind the arguments all four share
 void rec_launch_lds(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q, uint32_t n_lds) {
@@ -256,9 +270,9 @@ void rec_launch_lds(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q, ui
                        x.ctl.p, x.lds_list.p, x.tlg.p, q.off, q.items, ending...);
   };
   switch (q.end) {
-    case RecEnd::TopK:    launch(REC_FS(q, k_rec_lds), q.k, q.ids, q.scores, q.counts, q.f); break;
+    case RecEnd::TopK:    REC_SC(q, launch, REC_FS(q, k_rec_lds), k_rec_lds_scoped, q.k, q.ids, q.scores, q.counts, q.f); break;
     case RecEnd::Rank:    launch(REC_FS(q, k_rec_lds_rank), q.rk, q.counts, q.f); break;
-    case RecEnd::Grouped: launch(REC_FS(q, k_rec_lds_grouped), q.k, q.ids, q.scores, q.counts, q.f, q.gr); break;
+    case RecEnd::Grouped: REC_SC(q, launch, REC_FS(q, k_rec_lds_grouped), k_rec_lds_grouped_scoped, q.k, q.ids, q.scores, q.counts, q.f, q.gr); break;
     case RecEnd::Deep:    launch(REC_FS(q, k_rec_lds_deep), q.k, q.ids, q.scores, q.counts, q.f); break;
   }
 }
@@ -281,7 +295,8 @@ void rec_launch_tail(RecScratch& x, hipStream_t s, const RecReq& q, const RecGl&
 }
 
 // the whole call on stream s, every array of q on the device; returns with the work enqueued (after one synchronising read-back).
-// -1 (nothing but k_rec_bound has run) for a bad weight, which only a request with a filter can have; 0 otherwise.
+// -1 (nothing but k_rec_bound and k_rec_scope_bound has run) for a bad weight or an over-long scope list, which only a request with a filter can have; 0
+// otherwise.
 int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
   DirSlot* dir = m->d_dir;
   const uint32_t dmask = m->dir_size - 1, n = q.n;
@@ -290,6 +305,7 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
   HIP_OK(hipMemsetAsync(x.ctl.p, 0, sizeof(RecCtl), s));
   hipLaunchKernelGGL(REC_F(q, k_rec_bound), dim3(std::min<uint32_t>(blocks_for((uint64_t)n * 64), 16384)), dim3(256), 0, s, dir, dmask, n, q.off,
                      q.items, (uint64_t)(m->arena.mapped / 8), x.ctl.p, x.lds_list.p, x.tlg.p, x.big_list.p, x.big_off.p, q.counts, q.f);
+  if (q.scoped) hipLaunchKernelGGL(k_rec_scope_bound, dim3(std::min<uint32_t>(blocks_for(n), 16384)), dim3(256), 0, s, n, q.sc, x.ctl.p);
   HIP_OK(hipGetLastError());
   RecCtl c;
   HIP_OK(hipMemcpyAsync(&c, x.ctl.p, sizeof c, hipMemcpyDeviceToHost, s));
@@ -322,9 +338,10 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
       hipLaunchKernelGGL(k_rec_gl_plan, dim3(blocks_for(nt)), dim3(256), 0, s, G, dir, dmask, q.off, q.items, p0, nj, x.cnt.p);
       HIP_OK(hipGetLastError());
       rec_scan(x, s, x.cnt.p, nt, x.scan.p);
-      for (uint32_t j = 0; j < nj; j++)
-        hipLaunchKernelGGL(REC_FS(q, k_rec_gl_scan), dim3(2048), dim3(256), 0, s, G, dir, dmask, m->arena.base, q.off, q.items, p0, j, x.scan.p,
-                           q.f);
+      auto scan = [&](auto kernel, auto... args) {
+        hipLaunchKernelGGL(kernel, dim3(2048), dim3(256), 0, s, G, dir, dmask, m->arena.base, q.off, q.items, p0, args...);
+      };
+      for (uint32_t j = 0; j < nj; j++) REC_SC(q, scan, REC_FS(q, k_rec_gl_scan), k_rec_gl_scan_scoped, j, x.scan.p, q.f);
       HIP_OK(hipGetLastError());
     }
     rec_launch_tail(x, s, q, G, nseg);
@@ -334,17 +351,19 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
 }
 
 // behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session -- behind the grouped ending
-// k_rec_fill_grouped, the same under the request's quotas
+// k_rec_fill_grouped, the same under the request's quotas; for a scoped request k_rec_fill_scoped, which is both
 void rec_fill(hipStream_t s, const RecReq& q) {
   auto launch = [&](auto kernel, auto... quotas) {
     hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(blocks_for((uint64_t)q.n * 64), 16384)), dim3(256), 0, s, q.n, q.off, q.items, q.k,
                        q.fl.ids, (uint32_t)q.fl.n, q.ids, q.scores, q.counts, q.fl.n_scored, q.f, quotas...);
   };
-  if (q.end == RecEnd::Grouped) launch(k_rec_fill_grouped, q.gr);
+  if (q.scoped) launch(k_rec_fill_scoped, q.gr, q.sc);                   // (without quotas q.gr holds no id: k_rec_fill's walk)
+  else if (q.end == RecEnd::Grouped) launch(k_rec_fill_grouped, q.gr);
   else launch(k_rec_fill);
   HIP_OK(hipGetLastError());
 }
 
+#undef REC_SC
 #undef REC_FS
 #undef REC_F
 
@@ -375,6 +394,12 @@ RecReq rec_stage(RecCall& c, const RecReq& q) {
     HIP_OK(hipMemcpyAsync(x.h_grp.p, q.gr.of, q.gr.n * 4, hipMemcpyHostToDevice, c.s));
     d.gr.of = x.h_grp.p;
   }
+  if (q.scoped) {
+    x.h_scp.need(std::max<uint64_t>(q.sc.n, 1));
+    if (q.sc.n) HIP_OK(hipMemcpyAsync(x.h_scp.p, q.sc.of, q.sc.n * 4, hipMemcpyHostToDevice, c.s));
+    const RecList l = c.stage(n, q.sc.off, q.sc.gr, x.h_scoff, x.h_scgr);
+    d.sc = RecScope{x.h_scp.p, q.sc.n, l.off, l.val, q.sc.except};
+  }
   if (q.fl.n_scored) {
     const uint64_t one_list[2] = {0, q.fl.n};
     const RecList l = c.stage(1, one_list, q.fl.ids, x.h_foff, x.h_fill);
@@ -399,11 +424,20 @@ void rec_copy_back(RecCall& c, const RecReq& q, const RecReq& d) {
   if (q.fl.n_scored) HIP_OK(hipMemcpyAsync(q.fl.n_scored, d.fl.n_scored, n * 4, hipMemcpyDeviceToHost, c.s));
 }
 
-// Every session call behind its refusals.  No sessions: 0, and no scope.  A host flavour checks its weights before the device is
-// touched, so its driver result is 0; a _dev flavour's bad weight is found on the device: -1 through the same finish, and no fill.
+// ... and its scope lists: none longer than SMATRIX_SCOPE_MAX
+bool rec_host_scope_ok(const RecReq& q) {
+  if (q.scoped)
+    for (uint64_t s = 0; s < q.n; s++)
+      if (q.sc.off[s + 1] - q.sc.off[s] > REC_SCOPE_MAX) return false;
+  return true;
+}
+
+// Every session call behind its refusals.  No sessions: 0, and no scope.  A host flavour checks its weights and the lengths of its
+// scope lists before the device is touched, so its driver result is 0; a _dev flavour's bad weight or over-long list is found on the
+// device: -1 through the same finish, and no fill.
 int rec_call(smatrix_t* self, const RecReq& q, bool host, void* hip_stream = nullptr) {
   if (q.n == 0) return 0;
-  if (host && !rec_host_weights_ok(q.f.w, q.off, q.n)) return -1;
+  if (host && (!rec_host_weights_ok(q.f.w, q.off, q.n) || !rec_host_scope_ok(q))) return -1;
   RecCall c(self, host, hip_stream);
   const RecReq d = host ? rec_stage(c, q) : q;
   const int rc = rec_run(c.m, c.x(), c.s, d);
@@ -431,6 +465,15 @@ bool rec_fill_args_ok(const void* fill_ids, uint64_t n_fill, const void* n_score
 // ... the grouped call's map and quota
 bool rec_group_args_ok(const void* group_of, uint64_t group_n, uint32_t cap) {
   return cap != 0 && cap <= 64 && group_n <= (1ull << 32) && (group_of || group_n == 0);
+}
+
+// ... the scoped call's map, lists and mode: a map needs lists, lists come as a pair, and without lists nothing else is given
+static_assert(SMATRIX_SCOPE_MAX == REC_SCOPE_MAX, "the fill kernels of kernels/recommend.hpp hold a scope list one entry per lane");
+bool rec_scope_args_ok(const void* scope_of, uint64_t scope_n, const void* sc_offsets, const void* sc_groups, int scope_mode) {
+  if (scope_mode != SMATRIX_SCOPE_ONLY && scope_mode != SMATRIX_SCOPE_EXCEPT) return false;
+  if (scope_n > (1ull << 32) || (!scope_of && scope_n)) return false;
+  if ((sc_offsets == nullptr) != (sc_groups == nullptr)) return false;
+  return sc_offsets || (!scope_of && scope_n == 0);
 }
 
 void recommend_release(Matrix* m) {
@@ -555,6 +598,33 @@ int smatrix_cf_recommend_grouped_fill(smatrix_t* self, size_t n_sessions, const 
   return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
                                 RecEnd::Grouped, k, ids, scores, counts, RecRank{}, RecGroup{group_of, group_n, cap},
                                 RecFill{fill_ids, n_fill, n_scored}), true);
+}
+
+int smatrix_cf_recommend_scoped_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,
+                                    const double* d_weights, const uint64_t* d_ex_offsets, const uint32_t* d_ex_items,
+                                    const uint32_t* d_deny_bits, uint64_t deny_n, const uint32_t* d_scope_of, uint64_t scope_n,
+                                    const uint64_t* d_sc_offsets, const uint32_t* d_sc_groups, int scope_mode, const uint32_t* d_group_of,
+                                    uint64_t group_n, uint32_t cap, const uint32_t* d_fill_ids, uint64_t n_fill, int sim, double shrink,
+                                    uint32_t k, uint32_t* d_ids, double* d_scores, uint32_t* d_counts, uint32_t* d_n_scored, void* hip_stream) {
+  if (!rec_args_ok(n_sessions, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(d_group_of, group_n, cap) ||
+      !rec_fill_args_ok(d_fill_ids, n_fill, d_n_scored) || !rec_scope_args_ok(d_scope_of, scope_n, d_sc_offsets, d_sc_groups, scope_mode)) return -1;
+  return rec_call(self, rec_req(n_sessions, d_offsets, d_items, d_weights, d_ex_offsets, d_ex_items, d_deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, d_ids, d_scores, d_counts, RecRank{}, RecGroup{d_group_of, group_n, cap},
+                                RecFill{d_fill_ids, n_fill, d_n_scored},
+                                RecScope{d_scope_of, scope_n, d_sc_offsets, d_sc_groups, scope_mode == SMATRIX_SCOPE_EXCEPT ? 1u : 0u}), false, hip_stream);
+}
+
+int smatrix_cf_recommend_scoped(smatrix_t* self, size_t n_sessions, const uint64_t* offsets, const uint32_t* items, const double* weights,
+                                const uint64_t* ex_offsets, const uint32_t* ex_items, const uint32_t* deny_bits, uint64_t deny_n,
+                                const uint32_t* scope_of, uint64_t scope_n, const uint64_t* sc_offsets, const uint32_t* sc_groups, int scope_mode,
+                                const uint32_t* group_of, uint64_t group_n, uint32_t cap, const uint32_t* fill_ids, uint64_t n_fill, int sim,
+                                double shrink, uint32_t k, uint32_t* ids, double* scores, uint32_t* counts, uint32_t* n_scored) {
+  if (!rec_args_ok(n_sessions, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink) || !rec_k_ok(k) || !rec_group_args_ok(group_of, group_n, cap) ||
+      !rec_fill_args_ok(fill_ids, n_fill, n_scored) || !rec_scope_args_ok(scope_of, scope_n, sc_offsets, sc_groups, scope_mode)) return -1;
+  return rec_call(self, rec_req(n_sessions, offsets, items, weights, ex_offsets, ex_items, deny_bits, deny_n, sim, shrink,
+                                RecEnd::Grouped, k, ids, scores, counts, RecRank{}, RecGroup{group_of, group_n, cap},
+                                RecFill{fill_ids, n_fill, n_scored},
+                                RecScope{scope_of, scope_n, sc_offsets, sc_groups, scope_mode == SMATRIX_SCOPE_EXCEPT ? 1u : 0u}), true);
 }
 
 int smatrix_cf_recommend_deep_dev(smatrix_t* self, size_t n_sessions, const uint64_t* d_offsets, const uint32_t* d_items,

@@ -259,6 +259,44 @@ def _check_cap(cap):
         raise ValueError("cap must be an integer in 1 .. 64, not %r" % (cap,))
 
 
+SCOPE_MAX = 64                                           # include/smatrix_batch.h SMATRIX_SCOPE_MAX
+SCOPE_ONLY, SCOPE_EXCEPT = 0, 1                          # SMATRIX_SCOPE_ONLY, SMATRIX_SCOPE_EXCEPT
+_SCOPE_MODES = {"only": SCOPE_ONLY, "except": SCOPE_EXCEPT}
+
+
+def _scope_mode(mode):
+    try:
+        return _SCOPE_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError("mode must be 'only' or 'except', not %r" % (mode,)) from None
+
+
+def _scope_lists(scope, sessions):
+    """cf_recommend_scoped's scope -> (sc_offsets uint64[n+1], sc_groups uint32[total]), or (None, None) when no session is scoped:
+    one entry per session, None or a flat sequence of at most SCOPE_MAX integers in 0 .. 2**32 - 1.  Anything else is a ValueError"""
+    if scope is None or isinstance(scope, (str, bytes)) or not hasattr(scope, "__len__") or len(scope) != len(sessions):
+        raise ValueError("scope must hold one list of group ids (or None) per session")
+    lists = []
+    for one in scope:
+        if one is None:
+            one = ()
+        if isinstance(one, (str, bytes)) or not hasattr(one, "__len__"):
+            raise ValueError("a session's scope must be a sequence of group ids, not %r" % (one,))
+        if len(one) > SCOPE_MAX:
+            raise ValueError("a session's scope holds at most %d groups, not %d" % (SCOPE_MAX, len(one)))
+        a = np.asarray(one)
+        if a.size:
+            if a.ndim != 1 or a.dtype.kind not in "iu":
+                raise ValueError("a session's scope must hold integers in 0 .. 2**32 - 1")
+            wide = a.astype(np.int64 if a.dtype.kind == "i" else np.uint64)
+            if (wide < 0).any() or (wide > 0xFFFFFFFF).any():
+                raise ValueError("a session's scope must hold integers in 0 .. 2**32 - 1")
+        lists.append(a.astype(np.uint32).reshape(-1))
+    if not any(a.size for a in lists):
+        return None, None
+    return _sessions(lists)
+
+
 DEEP_MAX = 1024                                          # include/smatrix_batch.h SMATRIX_DEEP_MAX
 
 
@@ -632,6 +670,56 @@ class SparseMatrix:
                                                            cnt_ptr, n_scored_ptr, _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_recommend_grouped_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, fill, sim "
                              "or shrink")
+
+    def cf_recommend_scoped(self, sessions, k, scope_of, scope, mode="only", group_of=None, cap=None, fill=None, weights=None, exclude=None,
+                            deny=None, sim="cosine", shrink=0.0):
+        """cf_recommend_grouped_filled from these categories only (include/smatrix_batch.h smatrix_cf_recommend_scoped): a scope per
+        session, applied on the GPU where a candidate is made, before the cut at k.  scope_of: a second map as group_of (a uint32
+        sequence or a dict {id: group}; ids beyond its end and GROUP_NONE entries are ungrouped); scope: one list of at most SCOPE_MAX
+        group ids per session, None or [] for an unscoped session.  mode "only": a scoped session is given the ids whose group is in
+        its list and no ungrouped id; "except": every id but those.  An id out of scope is treated as an id of the session's
+        exclusion list.  group_of / cap (None: no quotas) and fill (None: no list) are cf_recommend_grouped_filled's.
+        -> (ids[n,k], scores[n,k] float64, counts[n], n_scored[n])"""
+        _check_k(k)
+        code = _scope_mode(mode)
+        if cap is None:
+            if group_of is not None:
+                raise ValueError("group_of needs a cap")
+            cap = 64
+        _check_cap(cap)
+        groups = _group_map(group_of)
+        scopes = _group_map(scope_of)
+        fill = _fill_ids(() if fill is None else fill)
+        sc_off, sc_gr = _scope_lists(scope, sessions)
+        if sc_off is None:
+            scopes = None                                                 # nobody is scoped: the C call takes a map with lists alone
+        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        ids, scores, counts = _topk_outputs(n, k)
+        n_scored = np.zeros(n, dtype=np.uint32)
+        if n and self._lib.smatrix_cf_recommend_scoped(*sess, *filt, _p(scopes), 0 if scopes is None else int(scopes.size), _p(sc_off, _lib.u64p),
+                                                       _p(sc_gr), code, _p(groups), 0 if groups is None else int(groups.size), int(cap),
+                                                       _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids), _p(scores, _DP),
+                                                       _p(counts), _p(n_scored)) != 0:
+            raise ValueError("smatrix_cf_recommend_scoped: bad k, n_sessions, weights, exclusion lists, deny bitmap, scope map, scope lists, "
+                             "mode, group map, cap, fill, sim or shrink")
+        return ids, scores, counts, n_scored
+
+    def cf_recommend_scoped_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, scope_ptr, scope_n,
+                                sc_off_ptr, sc_groups_ptr, mode, group_ptr, group_n, cap, fill_ptr, n_fill, sim, shrink, k, ids_ptr, scores_ptr,
+                                cnt_ptr, n_scored_ptr, stream=None):
+        """the same on device arrays (raw pointers, None for what is not given), the C order: cf_recommend_grouped_fill_dev's, and behind
+        deny_n scope uint32[scope_n], sc_off uint64[n+1], sc_groups uint32, mode "only" or "except".  A list longer than SCOPE_MAX
+        is found on the device: ValueError, the outputs' contents unspecified"""
+        _check_k(k)
+        _check_cap(cap)
+        scope_code = _scope_mode(mode)
+        code, h = _sim(sim), _shrink(shrink)
+        if self._lib.smatrix_cf_recommend_scoped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
+                                                     scope_ptr, scope_n, sc_off_ptr, sc_groups_ptr, scope_code, group_ptr, group_n, int(cap),
+                                                     fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr,
+                                                     _stream_ptr(stream)) != 0:
+            raise ValueError("smatrix_cf_recommend_scoped_dev: bad k, n, weights, exclusion lists, deny bitmap, scope map, scope lists, mode, "
+                             "group map, cap, fill, sim or shrink")
 
     def cf_recommend_deep(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_filtered with up to DEEP_MAX = 1024 results per session (include/smatrix_batch.h smatrix_cf_recommend_deep):
