@@ -30,13 +30,14 @@
 // rec_deep_table: up to REC_DEEP_MAX results, by a radix select of the k-th best key and a workgroup sort of what is at or above it.
 // smatrix_cf_recommend_fill (k_rec_fill, at the end of this file): the sim call's launches as they are, and one more behind them that
 // fills the free places of a short result from the caller's list under the session's own filters.
-// smatrix_cf_recommend_grouped_fill (k_rec_fill_grouped, behind k_rec_fill): the grouped call's launches as they are, and the fill under
-// the same quotas: the groups of the results live in lanes beside the ids, and a step's quota is decided by counts, without a walk.
+// smatrix_cf_recommend_grouped_fill (k_rec_fill_grouped, behind k_rec_fill): the grouped call's launches as they are, and the fill
+// under the same quotas: the groups of the results live in lanes beside the ids, and a step's quota is decided by counts.  It is
+// rec_fill_walk<false>, ONE body for the fill under quotas with and without a scope.
 // smatrix_cf_recommend_scoped (RecScope; k_rec_lds_scoped, k_rec_lds_grouped_scoped and k_rec_gl_scan_scoped, over the same bodies
-// with C set; k_rec_scope_bound and k_rec_fill_scoped at the end of this file): the grouped fill call with a per-session deny decided
-// by the id's group in a second map.  The test stands where rec_denied stands, on a claimed key of either tier -- once per distinct
-// key of a session --, and an out-of-scope key gets sqrt = -1 like a denied one, so the endings and the tables know nothing of it;
-// k_rec_fill_scoped tests the list's ids the same way.  The existing instances have C == false and keep their code.
+// with C set; k_rec_scope_bound and k_rec_fill_scoped = rec_fill_walk<true> at the end of this file): the grouped fill call
+// with a per-session deny decided by the id's group in a second map.  The test stands where rec_denied stands, on a claimed key of
+// either tier -- once per distinct key of a session --, and an out-of-scope key gets sqrt = -1 like a denied one, so the endings and
+// the tables know nothing of it; the walk tests the list's ids the same way.  The tiers' other instances have C == false.
 
 constexpr uint32_t REC_LDS_SLOTS = 4096;      // 4 + 8 + 8 bytes a slot: 80 KiB, two workgroups per CU (160 KiB)
 constexpr uint32_t REC_LDS_THREADS = 512;
@@ -1168,20 +1169,33 @@ __global__ __launch_bounds__(256) void k_rec_fill(uint32_t n, const uint64_t* __
   }
 }
 
-// ---- smatrix_cf_recommend_grouped_fill: the same behind the grouped ending, under its quotas ---------------------------------
-// k_rec_fill with the groups beside the ids: `mg` is the group of the result in `mine` (REC_GROUP_NONE in a free place), one gather
-// from gr.of per scored result at the start.  A step first finishes `ok` exactly as k_rec_fill does -- so of the lanes that hold
-// one id only the lowest is still ok, and a repeated id counts once --, then gathers the group of every lane still ok, g.  Lane i is a
-// SURVIVOR iff it is ungrouped or (the lanes j < have with mg_j == g) + (the ok lanes j < i with g_j == g) < cap: rec_group_table's
-// argument.  An ok lane of group g below i that is no survivor found the group full, and a full group stays full, so lane i finds it
-// full as well; and when every ok lane of group g below i survived, the sum IS the count of the serial walk.  Both counts come from
-// one more 64-step shuffle loop, over mg and g.  The survivors are numbered by mbcnt behind `have` and cut at the room left (the
-// session is full behind a cut: the lanes it drops decide nothing any more), and the id AND its group go to the lane that owns the
-// new place.  A step whose lanes are all refused -- 64 ids of full groups -- takes nothing and the walk goes on.
-__global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
-                                                          uint32_t k, const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids,
-                                                          double* scores, uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f,
-                                                          RecGroup gr) {
+// ---- the fill under quotas, and under a scope: ONE walk, rec_fill_walk<C>, and two kernels over it ---------------------------------
+// k_rec_fill_grouped (smatrix_cf_recommend_grouped_fill, <false>) and k_rec_fill_scoped (smatrix_cf_recommend_scoped, <true>); C is
+// the session's scope list in lanes and the scope test in front, every other line is shared.  k_rec_fill above is the same walk without
+// the groups, and stays written out: as an instance of this body it was measured slower ("One walk, two instances").
+// EVERY __shfl IS EXECUTED BY ALL 64 LANES, here and in k_rec_fill.  No shuffle stands on the right-hand side of && or ||, none in a
+// branch that is not wave-uniform: the only branches around shuffles are the template parameter, `nl != 0` (the session's, so the
+// wave's) and the __any / ballot exits.  A lane-dependent condition is applied to what the shuffle returned (`j < lane && o == fid`,
+// never `j < lane && __shfl(..)`): a shuffle reads garbage from a lane that does not execute it.
+// The step rule.  k_rec_fill's with the groups beside the ids: `mg` is the group of the result in `mine` (REC_GROUP_NONE in a free
+// place), one gather from gr.of per scored result at the start.  A step first finishes `ok` exactly as k_rec_fill does -- so of the
+// lanes that hold one id only the lowest is still ok, and a repeated id counts once --, then gathers the group of every lane still ok, g.
+// The survivors.  Lane i is a SURVIVOR iff it is ungrouped or (the lanes j < have with mg_j == g) + (the ok lanes j < i with g_j == g)
+// < cap: rec_group_table's argument.  An ok lane of group g below i that is no survivor found the group full, and a full group stays
+// full, so lane i finds it full as well; and when every ok lane of group g below i survived, the sum IS the count of the serial walk.
+// Both counts come from one more 64-step shuffle loop, over mg and g.  The survivors are numbered by mbcnt behind `have` and cut at the
+// room left (the session is full behind a cut: the lanes it drops decide nothing any more), and the id AND its group go to the lane
+// that owns the new place.  A step whose lanes are all refused -- 64 ids of full groups -- takes nothing and the walk goes on.
+// The scope (C).  An id out of the session's scope is an excluded id.  The wave holds the session's scope list one entry per lane,
+// `sl` -- hence REC_SCOPE_MAX = 64 --, REC_GROUP_NONE in the lanes beyond its end, and tests a step's 64 ids with one more 64-step
+// shuffle loop: lane i's id is LISTED iff its group in sc.of is not REC_GROUP_NONE and some lane's `sl` equals it.  The test is a
+// function of the id alone, like every test before the quotas, and stands first, so a step whose ids are all out of scope ends at the
+// first __any.  An unscoped session (an empty list) skips it: nl is the wave's.
+template <bool C>
+__device__ __forceinline__ void rec_fill_walk(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items, uint32_t k,
+                                              const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids, double* scores,
+                                              uint32_t* counts, uint32_t* __restrict__ n_scored, const RecFilt& f, const RecGroup& gr,
+                                              const RecScope& sc) {
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t s = wave; s < n; s += nwaves) {                     // (wave-uniform throughout: the shuffles need every lane)
@@ -1191,10 +1205,24 @@ __global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint
     const uint64_t b0 = off[s], L = off[s + 1] - b0;
     const uint64_t e0 = f.ex_off ? f.ex_off[s] : 0ull, E = f.ex_off ? f.ex_off[s + 1] - e0 : 0ull;
     uint32_t mine = lane < have ? ids[(uint64_t)s * k + lane] : 0u;
-    uint32_t mg = lane < have && mine < gr.n ? gr.of[mine] : REC_GROUP_NONE;
+    uint32_t mg = lane < have && mine < gr.n ? gr.of[mine] : REC_GROUP_NONE, nl = 0, sl = REC_GROUP_NONE;
+    if constexpr (C) {
+      uint64_t l0;
+      nl = rec_scope_len(sc, s, &l0);
+      sl = lane < nl ? sc.gr[l0 + lane] : REC_GROUP_NONE;
+    }
     for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
       const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
       bool ok = fid != 0 && !rec_denied(f, fid);
+      if constexpr (C) {
+        if (nl != 0) {
+          const uint32_t sg = ok && fid < sc.n ? sc.of[fid] : REC_GROUP_NONE;
+          bool listed = false;
+          for (uint32_t j = 0; j < 64; j++) listed |= (uint32_t)__shfl((int)sl, (int)j) == sg;
+          listed &= sg != REC_GROUP_NONE;                           // (an ungrouped id is listed nowhere: REC_GROUP_NONE matches nothing)
+          ok &= listed == (sc.except == 0);
+        }
+      }
       if (!__any(ok)) continue;
       for (uint64_t c0 = 0; c0 < L; c0 += 64) {
         const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)
@@ -1205,7 +1233,7 @@ __global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint
         for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
       }
       for (uint32_t j = 0; j < 64; j++) {
-        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);   // (every lane shuffles)
+        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);
         ok &= r != fid;                                             // in the result, scored or filled by an earlier step
         ok &= !(j < lane && o == fid);                              // a lane below holds the same id
       }
@@ -1227,14 +1255,22 @@ __global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint
       }
       const uint32_t to = take ? place : 0xffffffffu;               // ... and the lane that owns the place holds id and group from here on
       for (uint32_t j = 0; j < 64; j++) {
-        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j), og = (uint32_t)__shfl((int)g, (int)j);
-        if ((uint32_t)__shfl((int)to, (int)j) == lane) { mine = o; mg = og; }
+        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j), t = (uint32_t)__shfl((int)to, (int)j), og = (uint32_t)__shfl((int)g, (int)j);
+        if (t == lane) { mg = og; mine = o; }
       }
       const uint32_t room = k - have, found = (uint32_t)__popcll(m);
       have += found < room ? found : room;
     }
     if (lane == 0) counts[s] = have;
   }
+}
+
+// smatrix_cf_recommend_grouped_fill: the walk behind the grouped ending
+__global__ __launch_bounds__(256) void k_rec_fill_grouped(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
+                                                          uint32_t k, const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids,
+                                                          double* scores, uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f,
+                                                          RecGroup gr) {
+  rec_fill_walk<false>(n, off, items, k, fill, n_fill, ids, scores, counts, n_scored, f, gr, RecScope{});
 }
 
 // ---- smatrix_cf_recommend_scoped: the lists measured, and the fill under a scope -----------------------------------------------
@@ -1243,79 +1279,10 @@ __global__ __launch_bounds__(256) void k_rec_scope_bound(uint32_t n, RecScope sc
   for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (uint64_t)gridDim.x * blockDim.x)
     if (sc.off[s + 1] - sc.off[s] > REC_SCOPE_MAX) ctl->bad = 1u;
 }
-
-// k_rec_fill_grouped with the scope test: an id out of the session's scope is an excluded id.  The wave holds the session's scope
-// list one entry per lane, `sl` -- hence REC_SCOPE_MAX = 64 --, REC_GROUP_NONE in the lanes beyond its end, and tests a step's 64 ids
-// with one more 64-step shuffle loop, every lane shuffling: lane i's id is LISTED iff its group in sc.of is not REC_GROUP_NONE and
-// some lane's `sl` equals it.  The test is a function of the id alone, like every test before the quotas, and stands first, so a step
-// whose ids are all out of scope ends at the first __any.  An unscoped session (an empty list) skips it: nl is the wave's.
-// It is also the scoped fill WITHOUT quotas: under a RecGroup of no ids every lane is ungrouped, every ok lane a survivor, and the
-// kernel writes k_rec_fill's bytes.  Written out beside the two fill kernels, which keep their code.
+// the walk under a scope; WITHOUT quotas too: under a RecGroup of no ids every ok lane survives, and it writes k_rec_fill's bytes
 __global__ __launch_bounds__(256) void k_rec_fill_scoped(uint32_t n, const uint64_t* __restrict__ off, const uint32_t* __restrict__ items,
                                                          uint32_t k, const uint32_t* __restrict__ fill, uint32_t n_fill, uint32_t* ids,
                                                          double* scores, uint32_t* counts, uint32_t* __restrict__ n_scored, RecFilt f,
                                                          RecGroup gr, RecScope sc) {
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t s = wave; s < n; s += nwaves) {                     // (wave-uniform throughout: the shuffles need every lane)
-    uint32_t have = counts[s];
-    if (lane == 0) n_scored[s] = have;
-    if (have >= k || n_fill == 0) continue;
-    const uint64_t b0 = off[s], L = off[s + 1] - b0;
-    const uint64_t e0 = f.ex_off ? f.ex_off[s] : 0ull, E = f.ex_off ? f.ex_off[s + 1] - e0 : 0ull;
-    uint32_t mine = lane < have ? ids[(uint64_t)s * k + lane] : 0u;
-    uint32_t mg = lane < have && mine < gr.n ? gr.of[mine] : REC_GROUP_NONE;
-    uint64_t l0;
-    const uint32_t nl = rec_scope_len(sc, s, &l0);
-    const uint32_t sl = lane < nl ? sc.gr[l0 + lane] : REC_GROUP_NONE;
-    for (uint32_t j0 = 0; j0 < n_fill && have < k; j0 += 64) {
-      const uint32_t fid = j0 + lane < n_fill ? fill[j0 + lane] : 0u;
-      bool ok = fid != 0 && !rec_denied(f, fid);
-      if (nl != 0) {
-        const uint32_t sg = ok && fid < sc.n ? sc.of[fid] : REC_GROUP_NONE;
-        bool listed = false;
-        for (uint32_t j = 0; j < 64; j++) listed |= (uint32_t)__shfl((int)sl, (int)j) == sg;   // (every lane shuffles)
-        listed &= sg != REC_GROUP_NONE;                             // (an ungrouped id is listed nowhere: REC_GROUP_NONE matches nothing)
-        ok &= listed == (sc.except == 0);
-      }
-      if (!__any(ok)) continue;
-      for (uint64_t c0 = 0; c0 < L; c0 += 64) {
-        const uint32_t e = c0 + lane < L ? items[b0 + c0 + lane] : 0u;   // (a 0 beyond the end meets no id that is still ok)
-        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
-      }
-      for (uint64_t c0 = 0; c0 < E; c0 += 64) {
-        const uint32_t e = c0 + lane < E ? f.ex[e0 + c0 + lane] : 0u;
-        for (uint32_t j = 0; j < 64; j++) ok &= (uint32_t)__shfl((int)e, (int)j) != fid;
-      }
-      for (uint32_t j = 0; j < 64; j++) {
-        const uint32_t r = (uint32_t)__shfl((int)mine, (int)j), o = (uint32_t)__shfl((int)fid, (int)j);   // (every lane shuffles)
-        ok &= r != fid;                                             // in the result, scored or filled by an earlier step
-        ok &= !(j < lane && o == fid);                              // a lane below holds the same id
-      }
-      if (!__any(ok)) continue;
-      const uint32_t g = ok && fid < gr.n ? gr.of[fid] : REC_GROUP_NONE;   // (a lane that is not ok is in no group: it counts for nobody)
-      uint32_t same = 0;
-      for (uint32_t j = 0; j < 64; j++) {
-        const uint32_t r = (uint32_t)__shfl((int)mg, (int)j), o = (uint32_t)__shfl((int)g, (int)j);
-        same += (r == g ? 1u : 0u) + (j < lane && o == g ? 1u : 0u);
-      }
-      const bool sv = ok && (g == REC_GROUP_NONE || same < gr.cap);
-      const uint64_t m = __ballot(sv);
-      if (m == 0) continue;
-      const uint32_t place = have + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      const bool take = sv && place < k;                            // the room left is the cut
-      if (take) {
-        ids[(uint64_t)s * k + place] = fid;
-        scores[(uint64_t)s * k + place] = 0.0;
-      }
-      const uint32_t to = take ? place : 0xffffffffu;               // ... and the lane that owns the place holds id and group from here on
-      for (uint32_t j = 0; j < 64; j++) {
-        const uint32_t o = (uint32_t)__shfl((int)fid, (int)j), og = (uint32_t)__shfl((int)g, (int)j);
-        if ((uint32_t)__shfl((int)to, (int)j) == lane) { mine = o; mg = og; }
-      }
-      const uint32_t room = k - have, found = (uint32_t)__popcll(m);
-      have += found < room ? found : room;
-    }
-    if (lane == 0) counts[s] = have;
-  }
+  rec_fill_walk<true>(n, off, items, k, fill, n_fill, ids, scores, counts, n_scored, f, gr, sc);
 }

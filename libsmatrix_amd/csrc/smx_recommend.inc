@@ -37,8 +37,7 @@
 // with nothing given; the sim call with SMATRIX_SIM_COSINE and shrink 0 IS the filtered call; the grouped call with no map, or with a
 // quota that cannot bind (cap >= k), and the deep call with k <= 64 ARE the sim call, through the same launches.
 // The fill call (smatrix_cf_recommend_fill / _dev) is the sim call with ONE launch behind the driver's, rec_fill: k_rec_fill reads
-// the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).
-// The grouped fill call (smatrix_cf_recommend_grouped_fill / _dev) is the grouped call with that launch behind it: a request with a
+// the ids and counts both tiers wrote, notes them as n_scored and fills the free places from the caller's list (RecFill).// The grouped fill call (smatrix_cf_recommend_grouped_fill / _dev) is the grouped call with that launch behind it: a request with a
 // RecGroup AND a RecFill.  Where the map binds, rec_fill launches k_rec_fill_grouped, the fill under the same quotas; where it cannot,
 // rec_req has made the request the fill call's, k_rec_fill included.
 // The scoped call (smatrix_cf_recommend_scoped / _dev) is the grouped fill call with a RecScope.  With lists given, the kernels that
@@ -351,7 +350,8 @@ int rec_run(Matrix* m, RecScratch& x, hipStream_t s, const RecReq& q) {
 }
 
 // behind the recommend launches of both tiers, whatever they were: k_rec_fill, a wave per session -- behind the grouped ending
-// k_rec_fill_grouped, the same under the request's quotas; for a scoped request k_rec_fill_scoped, which is both
+// k_rec_fill_grouped, the same under the request's quotas; for a scoped request k_rec_fill_scoped, which is both (the two are
+// instances of one device body, rec_fill_walk<scope>)
 void rec_fill(hipStream_t s, const RecReq& q) {
   auto launch = [&](auto kernel, auto... quotas) {
     hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>(blocks_for((uint64_t)q.n * 64), 16384)), dim3(256), 0, s, q.n, q.off, q.items, q.k,

@@ -332,6 +332,19 @@ def _topk_outputs(n, k):
     return np.zeros((n, k), dtype=np.uint32), np.zeros((n, k), dtype=np.float64), np.zeros(n, dtype=np.uint32)
 
 
+def _map_args(m):
+    """a checked group or scope map (_group_map's) as the C calls take it: (map, map_n), (NULL, 0) for none"""
+    return _p(m), 0 if m is None else int(m.size)
+
+
+def _fill_args(fill):
+    """a checked fill list (_fill_ids') as the C calls take it: (fill_ids, n_fill), (NULL, 0) for an empty one"""
+    return _p(fill) if fill.size else None, int(fill.size)
+
+
+_DEV_BAD = "bad k, n, weights, exclusion lists, deny bitmap, "      # how the _dev recommend calls' refusals begin
+
+
 def _stream_ptr(stream):
     """a _dev method's stream as the C call takes it: a torch.cuda.Stream's handle, or a hipStream_t as int or None as they are"""
     return getattr(stream, "cuda_stream", stream)
@@ -499,8 +512,8 @@ class SparseMatrix:
         """the same on device arrays (raw pointers): offsets uint64[n+1], items uint32, ids uint32[n*k], scores float64[n*k],
         counts uint32[n].  stream: a torch.cuda.Stream or a hipStream_t as int (None: the legacy default stream, synchronised)"""
         _check_k(k)
-        if self._lib.smatrix_cf_recommend_batch_dev(self._h, n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_batch_dev: k must be 1..64 and n < 2^32")
+        self._cf_recommend_dev("smatrix_cf_recommend_batch_dev", "k must be 1..64 and n < 2^32",
+                               (n, off_ptr, items_ptr, k, ids_ptr, scores_ptr, cnt_ptr), stream)
 
     def _cf_front(self, sessions, weights, exclude, deny, sim, shrink, targets=None):
         """what cf_recommend_filtered, cf_rank and cf_explain do before their call: the arguments checked (every check before any
@@ -530,15 +543,31 @@ class SparseMatrix:
         sqrt(A) * sqrt(B) ("cosine"), A + B - cc ("jaccard") or A * B ("lift") over the totals A = self[a, 0], B = self[b, 0];
         shrink is a finite number >= 0.  The defaults make the call above"""
         _check_k(k)
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
+        front = (sessions, weights, exclude, deny, sim, shrink)
+        if (_sim(sim), _shrink(shrink)) != (0, 0.0):
+            return self._cf_recommend("smatrix_cf_recommend_sim", front, k)
+        n, _, sess, filt, _, _, _ = self._cf_front(*front)
         ids, scores, counts = _topk_outputs(n, k)
-        back = (k, _p(ids), _p(scores, _DP), _p(counts))
-        if measure == (0, 0.0):
-            if n and self._lib.smatrix_cf_recommend_filtered(*sess, *filt, *back) != 0:
-                raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
-        elif n and self._lib.smatrix_cf_recommend_sim(*sess, *filt, *measure, *back) != 0:
-            raise ValueError("smatrix_cf_recommend_sim: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
+        if n and self._lib.smatrix_cf_recommend_filtered(*sess, *filt, k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
+            raise ValueError("smatrix_cf_recommend_filtered: bad k, n_sessions, weights, exclusion lists or deny bitmap")
         return ids, scores, counts
+
+    def _cf_recommend(self, sym, front, k, extra=(), words="sim or shrink", n_scored=False):
+        """the host flavour of every recommend call that takes a measure, behind its own checks: `front` is _cf_front's arguments,
+        `extra` the checked C arguments between deny_n and the measure (scope, group, fill, in that order), `words` what the
+        refusal names behind the deny bitmap.  -> (ids[n,k], scores[n,k] float64, counts[n]), and n_scored[n] where the call has it;
+        without sessions no library call"""
+        n, measure, sess, filt, _, _, _ = self._cf_front(*front)
+        out = _topk_outputs(n, k) + ((np.zeros(n, dtype=np.uint32),) if n_scored else ())
+        if n and getattr(self._lib, sym)(*sess, *filt, *extra, *measure, k, _p(out[0]), _p(out[1], _DP), *map(_p, out[2:])) != 0:
+            raise ValueError("%s: bad k, n_sessions, weights, exclusion lists, deny bitmap, %s" % (sym, words))
+        return out
+
+    def _cf_recommend_dev(self, sym, words, args, stream):
+        """the _dev flavour of a recommend call behind its own checks: `args` the C arguments between the handle and the stream,
+        `words` what the refusal says went wrong"""
+        if getattr(self._lib, sym)(self._h, *args, _stream_ptr(stream)) != 0:
+            raise ValueError("%s: %s" % (sym, words))
 
     def cf_recommend_filtered_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, k, ids_ptr,
                                   scores_ptr, cnt_ptr, stream=None):
@@ -546,18 +575,17 @@ class SparseMatrix:
         float64 per item, ex_off uint64[n+1], ex_items uint32, deny uint32[(deny_n + 31) / 32].  A bad weight is found on the
         device: ValueError, the outputs' contents unspecified"""
         _check_k(k)
-        if self._lib.smatrix_cf_recommend_filtered_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                       deny_n, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_filtered_dev: bad k, n, weights, exclusion lists or deny bitmap")
+        self._cf_recommend_dev("smatrix_cf_recommend_filtered_dev", "bad k, n, weights, exclusion lists or deny bitmap",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, k, ids_ptr, scores_ptr, cnt_ptr),
+                               stream)
 
     def cf_recommend_sim_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, k,
                              ids_ptr, scores_ptr, cnt_ptr, stream=None):
         """cf_recommend_filtered_dev with cf_recommend_filtered's sim and shrink (smatrix_cf_recommend_sim_dev)"""
         _check_k(k)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_sim_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                  deny_n, code, h, k, ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_sim_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_sim_dev", _DEV_BAD + "sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, _sim(sim), _shrink(shrink), k,
+                                ids_ptr, scores_ptr, cnt_ptr), stream)
 
     def cf_popular(self, n, deny=None, min_total=1):
         """the most popular items (include/smatrix_batch.h smatrix_cf_popular): the up to n <= POPULAR_MAX ids x != 0 with the
@@ -588,25 +616,17 @@ class SparseMatrix:
         -> (ids[n,k], scores[n,k] float64, counts[n], n_scored[n]): the first n_scored[s] entries of session s are
         cf_recommend_filtered's, the entries up to counts[s] are filled"""
         _check_k(k)
-        fill = _fill_ids(fill)
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids, scores, counts = _topk_outputs(n, k)
-        n_scored = np.zeros(n, dtype=np.uint32)
-        if n and self._lib.smatrix_cf_recommend_fill(*sess, *filt, _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids),
-                                                     _p(scores, _DP), _p(counts), _p(n_scored)) != 0:
-            raise ValueError("smatrix_cf_recommend_fill: bad k, n_sessions, weights, exclusion lists, deny bitmap, fill, sim or shrink")
-        return ids, scores, counts, n_scored
+        return self._cf_recommend("smatrix_cf_recommend_fill", (sessions, weights, exclude, deny, sim, shrink), k,
+                                  _fill_args(_fill_ids(fill)), "fill, sim or shrink", n_scored=True)
 
     def cf_recommend_fill_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, fill_ptr, n_fill, sim,
                               shrink, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, stream=None):
         """the same on device arrays (raw pointers, None for what is not given): cf_recommend_sim_dev's, and fill uint32[n_fill]
         (None with n_fill 0: no list), n_scored uint32[n]"""
         _check_k(k)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                   fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr,
-                                                   _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, fill, sim or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_fill_dev", _DEV_BAD + "fill, sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, fill_ptr, n_fill, _sim(sim),
+                                _shrink(shrink), k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr), stream)
 
     def cf_recommend_grouped(self, sessions, k, group_of, cap, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_filtered with at most `cap` results of a session from one group -- brand, category, seller -- (include/
@@ -617,13 +637,8 @@ class SparseMatrix:
         has k candidates and more"""
         _check_k(k)
         _check_cap(cap)
-        groups = _group_map(group_of)
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids, scores, counts = _topk_outputs(n, k)
-        if n and self._lib.smatrix_cf_recommend_grouped(*sess, *filt, _p(groups), 0 if groups is None else int(groups.size), int(cap), *measure,
-                                                        k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
-            raise ValueError("smatrix_cf_recommend_grouped: bad k, n_sessions, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
-        return ids, scores, counts
+        return self._cf_recommend("smatrix_cf_recommend_grouped", (sessions, weights, exclude, deny, sim, shrink), k,
+                                  (*_map_args(_group_map(group_of)), int(cap)), "group map, cap, sim or shrink")
 
     def cf_recommend_grouped_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n, cap,
                                  sim, shrink, k, ids_ptr, scores_ptr, cnt_ptr, stream=None):
@@ -631,11 +646,9 @@ class SparseMatrix:
         (None with group_n 0: no grouping)"""
         _check_k(k)
         _check_cap(cap)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_grouped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                      group_ptr, group_n, int(cap), code, h, k, ids_ptr, scores_ptr, cnt_ptr,
-                                                      _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_grouped_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, sim or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_grouped_dev", _DEV_BAD + "group map, cap, sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n, int(cap),
+                                _sim(sim), _shrink(shrink), k, ids_ptr, scores_ptr, cnt_ptr), stream)
 
     def cf_recommend_grouped_filled(self, sessions, k, group_of, cap, fill, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_grouped, then the free places of a short result filled from `fill` under the same quotas (include/
@@ -646,17 +659,9 @@ class SparseMatrix:
         s are cf_recommend_grouped's"""
         _check_k(k)
         _check_cap(cap)
-        groups = _group_map(group_of)
-        fill = _fill_ids(fill)
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids, scores, counts = _topk_outputs(n, k)
-        n_scored = np.zeros(n, dtype=np.uint32)
-        if n and self._lib.smatrix_cf_recommend_grouped_fill(*sess, *filt, _p(groups), 0 if groups is None else int(groups.size), int(cap),
-                                                             _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids),
-                                                             _p(scores, _DP), _p(counts), _p(n_scored)) != 0:
-            raise ValueError("smatrix_cf_recommend_grouped_fill: bad k, n_sessions, weights, exclusion lists, deny bitmap, group map, cap, fill, "
-                             "sim or shrink")
-        return ids, scores, counts, n_scored
+        return self._cf_recommend("smatrix_cf_recommend_grouped_fill", (sessions, weights, exclude, deny, sim, shrink), k,
+                                  (*_map_args(_group_map(group_of)), int(cap), *_fill_args(_fill_ids(fill))),
+                                  "group map, cap, fill, sim or shrink", n_scored=True)
 
     def cf_recommend_grouped_fill_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n,
                                       cap, fill_ptr, n_fill, sim, shrink, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr, stream=None):
@@ -664,12 +669,9 @@ class SparseMatrix:
         (None with n_fill 0: no list), n_scored uint32[n]"""
         _check_k(k)
         _check_cap(cap)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_grouped_fill_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                           group_ptr, group_n, int(cap), fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr,
-                                                           cnt_ptr, n_scored_ptr, _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_grouped_fill_dev: bad k, n, weights, exclusion lists, deny bitmap, group map, cap, fill, sim "
-                             "or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_grouped_fill_dev", _DEV_BAD + "group map, cap, fill, sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, group_ptr, group_n, int(cap),
+                                fill_ptr, n_fill, _sim(sim), _shrink(shrink), k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr), stream)
 
     def cf_recommend_scoped(self, sessions, k, scope_of, scope, mode="only", group_of=None, cap=None, fill=None, weights=None, exclude=None,
                             deny=None, sim="cosine", shrink=0.0):
@@ -693,16 +695,9 @@ class SparseMatrix:
         sc_off, sc_gr = _scope_lists(scope, sessions)
         if sc_off is None:
             scopes = None                                                 # nobody is scoped: the C call takes a map with lists alone
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids, scores, counts = _topk_outputs(n, k)
-        n_scored = np.zeros(n, dtype=np.uint32)
-        if n and self._lib.smatrix_cf_recommend_scoped(*sess, *filt, _p(scopes), 0 if scopes is None else int(scopes.size), _p(sc_off, _lib.u64p),
-                                                       _p(sc_gr), code, _p(groups), 0 if groups is None else int(groups.size), int(cap),
-                                                       _p(fill) if fill.size else None, int(fill.size), *measure, k, _p(ids), _p(scores, _DP),
-                                                       _p(counts), _p(n_scored)) != 0:
-            raise ValueError("smatrix_cf_recommend_scoped: bad k, n_sessions, weights, exclusion lists, deny bitmap, scope map, scope lists, "
-                             "mode, group map, cap, fill, sim or shrink")
-        return ids, scores, counts, n_scored
+        return self._cf_recommend("smatrix_cf_recommend_scoped", (sessions, weights, exclude, deny, sim, shrink), k,
+                                  (*_map_args(scopes), _p(sc_off, _lib.u64p), _p(sc_gr), code, *_map_args(groups), int(cap), *_fill_args(fill)),
+                                  "scope map, scope lists, mode, group map, cap, fill, sim or shrink", n_scored=True)
 
     def cf_recommend_scoped_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, scope_ptr, scope_n,
                                 sc_off_ptr, sc_groups_ptr, mode, group_ptr, group_n, cap, fill_ptr, n_fill, sim, shrink, k, ids_ptr, scores_ptr,
@@ -713,13 +708,10 @@ class SparseMatrix:
         _check_k(k)
         _check_cap(cap)
         scope_code = _scope_mode(mode)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_scoped_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n,
-                                                     scope_ptr, scope_n, sc_off_ptr, sc_groups_ptr, scope_code, group_ptr, group_n, int(cap),
-                                                     fill_ptr, n_fill, code, h, k, ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr,
-                                                     _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_scoped_dev: bad k, n, weights, exclusion lists, deny bitmap, scope map, scope lists, mode, "
-                             "group map, cap, fill, sim or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_scoped_dev", _DEV_BAD + "scope map, scope lists, mode, group map, cap, fill, sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, scope_ptr, scope_n, sc_off_ptr,
+                                sc_groups_ptr, scope_code, group_ptr, group_n, int(cap), fill_ptr, n_fill, _sim(sim), _shrink(shrink), k,
+                                ids_ptr, scores_ptr, cnt_ptr, n_scored_ptr), stream)
 
     def cf_recommend_deep(self, sessions, k, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_filtered with up to DEEP_MAX = 1024 results per session (include/smatrix_batch.h smatrix_cf_recommend_deep):
@@ -727,22 +719,16 @@ class SparseMatrix:
         cf_recommend_filtered's but k, an integer in 1 .. DEEP_MAX.  -> (ids[n,k], scores[n,k] float64, counts[n]) as there: the
         first 64 entries of a session are cf_recommend_filtered's with k = 64, and cf_rank answers ids[s, r] with the rank r"""
         _check_deep_k(k)
-        k = int(k)
-        n, measure, sess, filt, _, _, _ = self._cf_front(sessions, weights, exclude, deny, sim, shrink)
-        ids, scores, counts = _topk_outputs(n, k)
-        if n and self._lib.smatrix_cf_recommend_deep(*sess, *filt, *measure, k, _p(ids), _p(scores, _DP), _p(counts)) != 0:
-            raise ValueError("smatrix_cf_recommend_deep: bad k, n_sessions, weights, exclusion lists, deny bitmap, sim or shrink")
-        return ids, scores, counts
+        return self._cf_recommend("smatrix_cf_recommend_deep", (sessions, weights, exclude, deny, sim, shrink), int(k))
 
     def cf_recommend_deep_dev(self, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, sim, shrink, k,
                               ids_ptr, scores_ptr, cnt_ptr, stream=None):
         """the same on device arrays (raw pointers, None for what is not given): cf_recommend_sim_dev's, with k up to DEEP_MAX;
         ids uint32[n*k], scores float64[n*k]"""
         _check_deep_k(k)
-        code, h = _sim(sim), _shrink(shrink)
-        if self._lib.smatrix_cf_recommend_deep_dev(self._h, n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr,
-                                                   deny_n, code, h, int(k), ids_ptr, scores_ptr, cnt_ptr, _stream_ptr(stream)) != 0:
-            raise ValueError("smatrix_cf_recommend_deep_dev: bad k, n, weights, exclusion lists, deny bitmap, sim or shrink")
+        self._cf_recommend_dev("smatrix_cf_recommend_deep_dev", _DEV_BAD + "sim or shrink",
+                               (n, off_ptr, items_ptr, weights_ptr, ex_off_ptr, ex_items_ptr, deny_ptr, deny_n, _sim(sim), _shrink(shrink), int(k),
+                                ids_ptr, scores_ptr, cnt_ptr), stream)
 
     def cf_rank(self, sessions, targets, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """where given items land in each session's ranking (include/smatrix_batch.h smatrix_cf_rank): cf_recommend_filtered's

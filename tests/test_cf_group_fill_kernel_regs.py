@@ -3,10 +3,11 @@ register, scalar or vector, uses no scratch memory, and keeps the register count
 counts are read from the gfx950 code object in smatrix.so through tools/kernel_regs.py, as tests/test_cf_fill_kernel_regs.py does).
 
 VGPRs of that build, and the bound: the count rounded up to the granule of 8 registers (512 per SIMD):
-    k_rec_fill_grouped   55 -> 56    a wave per session; k_rec_fill's loops and one more 64-step shuffle loop for the two counts, the
+    k_rec_fill_grouped   56 -> 56    a wave per session; k_rec_fill's loops and one more 64-step shuffle loop for the two counts, the
                                      groups of the result in one more register per lane: 8 waves per SIMD, as k_rec_fill (61 -> 64)
-The kernel is written out beside k_rec_fill, which it leaves alone: tests/test_cf_fill_kernel_regs.py, unchanged, pins k_rec_fill at 64
-and no spill, and the other register tests pin the rest."""
+The kernel is rec_fill_walk<false>, the body it shares with k_rec_fill_scoped (written out on its own it was 55).  k_rec_fill stays
+written out beside it: tests/test_cf_fill_kernel_regs.py, unchanged, pins k_rec_fill at 64 and no spill, and the other register tests
+pin the rest."""
 from tests.test_merge_sim_kernel_regs import counts
 
 NEW = {"smx::k_rec_fill_grouped": 56}

@@ -314,6 +314,13 @@ def test_no_scope_is_the_grouped_fill_call(world):
     got = w.m.cf_recommend_scoped(sessions, 10, None, [None] * len(sessions), sim="jaccard", shrink=10.0, **kw)
     sim_call = w.m.cf_recommend_filtered(sessions, 10, sim="jaccard", shrink=10.0, **kw)
     assert same_bytes(got[:3], sim_call) and got[3].tobytes() == got[2].tobytes()
+    # one scoped session, no quotas: the scoped fill kernel against the plain one, which is given what the scope keeps out as a list
+    one = [l if s == 11 else [] for s, l in enumerate(S.scope_lists(sessions, seed=9))]
+    for k in (10, 64):
+        got = w.m.cf_recommend_scoped(sessions, k, ARR, one, "only", fill=GF.fill_list(), **kw)
+        want = w.m.cf_recommend_filled(sessions, k, GF.fill_list(), exclude=extended(sessions, one, "only", exclude=exclude), deny=F.DENY)
+        assert one[11] and 0 < got[3][11] < got[2][11]                    # the session is scoped, scores some results and fills some
+        assert same_bytes(got, want), k
 
 
 # ---- 9: offsets that do not start at 0 ---------------------------------------------------------------------------------------------------
