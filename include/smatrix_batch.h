@@ -367,6 +367,49 @@ int smatrix_cf_popular(smatrix_t* self, const uint32_t* deny_bits, uint64_t deny
 int smatrix_cf_popular_dev(smatrix_t* self, const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t min_total,
                            uint32_t n, uint32_t* d_ids, uint32_t* d_totals, uint32_t* d_n_found, void* hip_stream);
 
+/* The trending items: the n ids whose totals (column 0) in `now` grew most against a scaled baseline taken from a second matrix,
+ * `base` -- the matrix of an older window, as smatrix_cf_import_events / smatrix_merge_scaled leave one --, joined and selected on
+ * the GPU with no export of either matrix.  The ids are a fill list for smatrix_cf_recommend_fill as they stand.
+ *   candidates every id x != 0 for which smatrix_row_info(now, x) returns 1, x not denied, with
+ *                T = smatrix_get(now, x, 0) >= max(min_total, 1);
+ *                B = smatrix_get(base, x, 0): 0 for an id without a row in base, a row without a head pair, or a head decremented to 0;
+ *                E = floor(B * num / den), computed in 64 bits: smatrix_merge_scaled's transform, with its 1 <= num <= den;
+ *                T > E, and the gain G = T - E >= max(min_gain, 1).
+ *              The deny bitmap is smatrix_cf_recommend_filtered's, bit for bit.  An id that only base holds is no candidate.
+ *   score      an IEEE double; G and E are converted exactly and each operation is rounded on its own (no fused multiply-add):
+ *                D = (double)E + shrink; if (D == 0.0) D = 1.0;      (a new item with shrink == 0: the read path's tb == 0 -> 1)
+ *                SMATRIX_TREND_GAIN    (double)G          absolute gain: mostly hands back the popular items
+ *                SMATRIX_TREND_RATIO   G / D              relative growth, smoothed by shrink
+ *                SMATRIX_TREND_ZSCORE  G / sqrt(D)        a Poisson z-score with smoothing
+ *              Every candidate's score is finite and greater than 0.
+ *   order      score descending, equal scores by ascending id: the key RkCosine::make(x, score bits) of kernels/rank_key.hpp.  Keys
+ *              are unique, so the result depends on the two matrices' contents alone, not on directory order, insertion history
+ *              or growth.
+ *   output     the min(n, candidates) best, best first: ids[i], scores[i], totals[i] = T, expected[i] = E, *n_found their number
+ *              (DEVICE pointers in _dev).  n <= SMATRIX_POPULAR_MAX.  The host flavour zero-fills the unused entries; _dev leaves them.
+ * Returns -1, outputs as they were and the device untouched, for n == 0 or n > SMATRIX_POPULAR_MAX; base NULL, base == now or the two
+ * matrices on different devices; num == 0, den == 0 or num > den; an unknown measure; shrink negative, NaN or infinite (-0.0 acts
+ * as 0.0); deny_n > 2^32, or deny_bits NULL with deny_n != 0; any output pointer NULL.  0 otherwise, an empty `now` included
+ * (n_found = 0).
+ * How: smatrix_cf_popular's steps over 96-bit keys.  A key per slot of now's directory (one head-cell gather and ONE look-up of the
+ * id in base's directory per row), a device-wide MSB radix select of up to 12 byte passes from the highest byte in which the keys
+ * differ, the keys at or above the threshold collected with one atomic add per workgroup, one workgroup that sorts them in LDS
+ * and looks T and E up again for the entries it stores.  _dev makes no read-back at all.  Scratch (now's read-path scratch): 12
+ * bytes per slot of now's directory, 12 n bytes and a control block of 13 KiB.
+ * Locks, mirrors, streams: BOTH matrix locks are held for the call, taken in address order (smatrix_merge's rule: this call and a
+ * merge of the same two matrices cannot wait for each other); scalar writes still in either host mirror are written back first;
+ * the scratch is ordered behind the previous read-path call on `now` whatever its stream.  hip_stream == NULL synchronises.  _dev
+ * with a stream returns with its work enqueued: NEITHER matrix may be written or closed until the stream has passed that work.
+ * Neither matrix is modified; file-backed matrices work unchanged.  Deterministic. */
+enum { SMATRIX_TREND_GAIN = 0, SMATRIX_TREND_RATIO = 1, SMATRIX_TREND_ZSCORE = 2 };
+int smatrix_cf_trending(smatrix_t* now, smatrix_t* base, int measure, uint32_t num, uint32_t den, double shrink,
+                        const uint32_t* deny_bits, uint64_t deny_n, uint32_t min_total, uint32_t min_gain, uint32_t n,
+                        uint32_t* ids, double* scores, uint32_t* totals, uint32_t* expected, uint32_t* n_found);
+int smatrix_cf_trending_dev(smatrix_t* now, smatrix_t* base, int measure, uint32_t num, uint32_t den, double shrink,
+                            const uint32_t* d_deny_bits, uint64_t deny_n, uint32_t min_total, uint32_t min_gain, uint32_t n,
+                            uint32_t* d_ids, double* d_scores, uint32_t* d_totals, uint32_t* d_expected, uint32_t* d_n_found,
+                            void* hip_stream);
+
 /* k results for cold sessions: smatrix_cf_recommend_sim, then the free places of a short result filled from a list the caller
  * gives -- popular (smatrix_cf_popular), trending or editorial; the library does not care which -- under the session's own filters.
  * A new visitor, a session of long-tail items or one whose candidates are mostly excluded or denied still gets k results.

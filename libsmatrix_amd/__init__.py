@@ -9,5 +9,5 @@ The compute path is lib/smatrix.so (HIP); importing works without a GPU, opening
 matrix does not.
 """
 from .matrix import (DEEP_MAX, GROUP_NONE, IMPORT_FORWARD, IMPORT_NO_SELF, OP_DECR, OP_GET, OP_INCR, OP_SET, POPULAR_MAX, RANK_NONE, SCOPE_EXCEPT, SCOPE_MAX,  # noqa: F401
-                     SCOPE_ONLY, SparseMatrix, device_available, explain_table, rank_metrics)
+                     SCOPE_ONLY, TREND_GAIN, TREND_RATIO, TREND_ZSCORE, SparseMatrix, device_available, explain_table, rank_metrics)
 from .stream import Stream  # noqa: F401

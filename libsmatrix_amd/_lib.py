@@ -87,6 +87,10 @@ def load():
         "smatrix_cf_explain_dev": (C.c_int, [H, C.c_size_t, V, V, V, C.c_int, C.c_double, V, V, V, C.c_uint64, V, V, V]),
         "smatrix_cf_popular": (C.c_int, [H, u32p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p]),
         "smatrix_cf_popular_dev": (C.c_int, [H, V, C.c_uint64, C.c_uint32, C.c_uint32, V, V, V, V]),
+        "smatrix_cf_trending": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_double, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          u32p, C.POINTER(C.c_double), u32p, u32p, u32p]),
+        "smatrix_cf_trending_dev": (C.c_int, [H, H, C.c_int, C.c_uint32, C.c_uint32, C.c_double, V, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              V, V, V, V, V, V]),
         "smatrix_cf_recommend_fill": (C.c_int, [H, C.c_size_t, u64p, u32p, C.POINTER(C.c_double), u64p, u32p, u32p, C.c_uint64, u32p, C.c_uint64,
                                                 C.c_int, C.c_double, C.c_uint32, u32p, C.POINTER(C.c_double), u32p, u32p]),
         "smatrix_cf_recommend_fill_dev": (C.c_int, [H, C.c_size_t, V, V, V, V, V, V, C.c_uint64, V, C.c_uint64, C.c_int, C.c_double, C.c_uint32,

@@ -37,6 +37,7 @@ namespace smx {
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
 #include "kernels/popular.hpp"
+#include "kernels/trending.hpp"
 #include "kernels/explain.hpp"
 #include "kernels/import_events.hpp"
 #include "kernels/io_router.hpp"

@@ -77,6 +77,8 @@ struct RecScratch {
   DevBuf<uint64_t> h_scoff;
   DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
   DevBuf<unsigned long long> p_keys, p_out;          // directory slot, the n keys collected (ids: h_ids, totals: h_counts, n: h_nsc)
+  DevBuf<SelCtl<RkCosine>> t_ctl;                    // ... and the trending call's (smx_trending.inc): the select's state, three words
+  DevBuf<uint32_t> t_keys, t_out;                    // per slot of the directory, per key collected (its answers: h_ids, h_scores, h_counts, h_ranks, h_nsc)
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
   // EVERY buffer above, and the only list of them: the trim, the "any buffer big" test and the release are this visitor's
   template <typename Fn>
@@ -84,7 +86,7 @@ struct RecScratch {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
     f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(h_grp); f(h_scp); f(h_scgr); f(h_scoff);
-    f(p_ctl); f(p_keys); f(p_out);
+    f(p_ctl); f(p_keys); f(p_out); f(t_ctl); f(t_keys); f(t_out);
   }
 };
 

@@ -3294,5 +3294,8 @@ void smx_stream_release_device(smx_stream_t* st) {
 // ---- the most popular items, for filling short results (smatrix_cf_popular) -------------------------
 #include "smx_popular.inc"
 
+// ---- the trending items: totals against a scaled baseline from a second matrix (smatrix_cf_trending) --
+#include "smx_trending.inc"
+
 // ---- the multi-GPU router (include/smatrix_shard.h) ---------------------------------------------------
 #include "smx_shard.inc"

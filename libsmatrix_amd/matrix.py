@@ -203,6 +203,28 @@ def _popular_args(n, min_total):
     _check_u32("min_total", min_total)
 
 
+TREND_GAIN, TREND_RATIO, TREND_ZSCORE = 0, 1, 2          # include/smatrix_batch.h SMATRIX_TREND_*
+_TRENDS = {"gain": TREND_GAIN, "ratio": TREND_RATIO, "zscore": TREND_ZSCORE}
+
+
+def _trend(measure):
+    """"gain" / "ratio" / "zscore" -> the measure's code; anything else is a ValueError"""
+    if isinstance(measure, str) and measure in _TRENDS:
+        return _TRENDS[measure]
+    raise ValueError("measure must be 'gain', 'ratio' or 'zscore', not %r" % (measure,))
+
+
+def _trending_args(base, n, measure, num, den, shrink, min_total, min_gain):
+    """cf_trending's arguments behind the matrix itself: base another SparseMatrix, n and min_total as cf_popular's, min_gain a
+    uint32, 1 <= num <= den as merge_scaled's -> (the measure's code, shrink as float); anything else is a ValueError"""
+    if not isinstance(base, SparseMatrix):
+        raise ValueError("base must be a SparseMatrix, not %r" % (base,))
+    _popular_args(n, min_total)
+    _check_u32("min_gain", min_gain)
+    _scale_args(num, den, 0)
+    return _trend(measure), _shrink(shrink)
+
+
 def _fill_ids(fill):
     """cf_recommend_filled's list -> uint32[n_fill]: a flat sequence of integers in 0 .. 2**32 - 1, which may be empty.  Anything
     else is a ValueError"""
@@ -608,6 +630,39 @@ class SparseMatrix:
         if self._lib.smatrix_cf_popular_dev(self._h, deny_ptr, deny_n, int(min_total), int(n), ids_ptr, totals_ptr, n_found_ptr,
                                             _stream_ptr(stream)) != 0:
             raise ValueError("smatrix_cf_popular_dev: bad n, deny bitmap or outputs")
+
+    def cf_trending(self, base, n, measure="zscore", num=1, den=1, shrink=0.0, deny=None, min_total=1, min_gain=1):
+        """the trending items (include/smatrix_batch.h smatrix_cf_trending): the up to n <= POPULAR_MAX ids x != 0 of this matrix
+        whose totals T = self[x, 0] >= max(min_total, 1) grew most against E = floor(base[x, 0] * num / den) -- `base` another
+        SparseMatrix, the older window --, by G = T - E >= max(min_gain, 1) ("gain"), G / D ("ratio") or G / sqrt(D) ("zscore") with
+        D = E + shrink (0 counted as 1); the ids of `deny` left out.  Joined and selected on the GPU over both matrices.
+        -> (ids uint32[n_found], scores float64[n_found], totals uint32[n_found], expected uint32[n_found]), score descending,
+        equal scores by ascending id"""
+        code, h = _trending_args(base, n, measure, num, den, shrink, min_total, min_gain)
+        if base is self:
+            raise ValueError("base must be another matrix than this one")
+        bits, deny_n = _deny_bitmap(deny) if deny is not None else (None, 0)
+        ids, scores = np.zeros(int(n), dtype=np.uint32), np.zeros(int(n), dtype=np.float64)
+        totals, expected = np.zeros(int(n), dtype=np.uint32), np.zeros(int(n), dtype=np.uint32)
+        found = C.c_uint32(0)
+        if self._lib.smatrix_cf_trending(self._h, base._h, code, int(num), int(den), h, _p(bits), deny_n, int(min_total), int(min_gain), int(n),
+                                         _p(ids), _p(scores, _DP), _p(totals), _p(expected), C.byref(found)) != 0:
+            raise ValueError("smatrix_cf_trending: bad base, n, num / den, shrink or deny bitmap")
+        f = found.value
+        return ids[:f].copy(), scores[:f].copy(), totals[:f].copy(), expected[:f].copy()
+
+    def cf_trending_dev(self, base, n, measure, num, den, shrink, deny_ptr, deny_n, min_total, min_gain, ids_ptr, scores_ptr, totals_ptr,
+                        expected_ptr, n_found_ptr, stream=None):
+        """the same on device arrays (raw pointers; deny_ptr None with deny_n 0 for no bitmap): deny uint32[(deny_n + 31) / 32],
+        ids uint32[n], scores float64[n], totals uint32[n], expected uint32[n], n_found uint32[1].  No read-back: nothing is returned,
+        the entries beyond n_found are left as they were.  With a stream the work is enqueued on return: neither matrix may be
+        written or closed until the stream has passed it"""
+        code, h = _trending_args(base, n, measure, num, den, shrink, min_total, min_gain)
+        if base is self:
+            raise ValueError("base must be another matrix than this one")
+        if self._lib.smatrix_cf_trending_dev(self._h, base._h, code, int(num), int(den), h, deny_ptr, deny_n, int(min_total), int(min_gain), int(n),
+                                             ids_ptr, scores_ptr, totals_ptr, expected_ptr, n_found_ptr, _stream_ptr(stream)) != 0:
+            raise ValueError("smatrix_cf_trending_dev: bad base, n, num / den, shrink, deny bitmap or outputs")
 
     def cf_recommend_filled(self, sessions, k, fill, weights=None, exclude=None, deny=None, sim="cosine", shrink=0.0):
         """cf_recommend_filtered, then the free places of a short result filled from `fill` (include/smatrix_batch.h
