@@ -36,6 +36,7 @@ namespace smx {
 #include "kernels/sim.hpp"
 #include "kernels/merge.hpp"
 #include "kernels/recommend.hpp"
+#include "kernels/select.hpp"
 #include "kernels/popular.hpp"
 #include "kernels/trending.hpp"
 #include "kernels/explain.hpp"

@@ -3,26 +3,41 @@
 // stage_filter: the deny bitmap is the filtered call's); the device code is kernels/popular.hpp.
 //
 // Inside a RecCall (the matrix lock, the scalar mirror written back, behind the previous read-path call's work; its finish applies
-// the recommend calls' synchronisation rule and trim), pop_run enqueues, with no read-back anywhere:
-//   k_pop_keys, k_pop_start, RkValue::DIGITS times (k_pop_hist, k_pop_pick), k_pop_collect, k_pop_sort
-// The select's state lives in PopCtl; a pass behind the one that finished it returns at its first load.  Scratch: 8 bytes per
-// directory slot (the keys), 8 n bytes (the keys collected), PopCtl.  The host flavour stages the bitmap and copies the answers back.
+// the recommend calls' synchronisation rule and trim), pop_run enqueues, with no read-back anywhere, k_pop_keys, the dense select
+// of kernels/select.hpp (sel_run, here because the trending call enqueues the same) and k_pop_sort.  Scratch: RecScratch's sel_*,
+// 8 bytes per directory slot (the keys), 8 n bytes (the keys collected), SelCtl.  The host flavour stages the bitmap and copies
+// the answers back.
 
 namespace {
 
+template <typename P>
+SelCtl<P>* sel_ctl(RecScratch& x) { return reinterpret_cast<SelCtl<P>*>(x.sel_ctl.p); }
+
+// The select over a key of type P per directory slot, from the key kernel to the collection: sizes the scratch, zeroes SelCtl<P>,
+// launch_keys(grid, keys, ctl), then k_sel_start, P::DIGITS times (k_sel_hist, k_sel_pick) -- a pass behind the one that finished
+// the select returns at its first load -- and k_sel_collect.  -> the min(n, candidates) keys collected (their number: SelCtl::n_out).
+template <typename P, typename Keys>
+const uint32_t* sel_run(RecScratch& x, hipStream_t s, uint32_t slots, uint32_t n, Keys launch_keys) {
+  const uint32_t grid = std::min<uint32_t>(blocks_for(slots), POP_GRID_MAX);
+  x.sel_ctl.need(sizeof(SelCtl<P>) / 4); x.sel_keys.need((size_t)slots * P::W); x.sel_out.need((size_t)n * P::W);
+  SelCtl<P>* ctl = sel_ctl<P>(x);
+  HIP_OK(hipMemsetAsync(ctl, 0, sizeof(SelCtl<P>), s));
+  launch_keys(grid, x.sel_keys.p, ctl);
+  hipLaunchKernelGGL(k_sel_start<P>, dim3(1), dim3(64), 0, s, ctl, n);
+  for (uint32_t pass = 0; pass < P::DIGITS; pass++) {
+    hipLaunchKernelGGL(k_sel_hist<P>, dim3(grid), dim3(256), 0, s, x.sel_keys.p, slots, ctl, pass);
+    hipLaunchKernelGGL(k_sel_pick<P>, dim3(1), dim3(64), 0, s, ctl, pass);
+  }
+  hipLaunchKernelGGL(k_sel_collect<P>, dim3(grid), dim3(256), 0, s, x.sel_keys.p, slots, ctl, n, x.sel_out.p);
+  return x.sel_out.p;
+}
+
 void pop_run(Matrix* m, RecScratch& x, hipStream_t s, const RecFilt& f, uint32_t min_total, uint32_t n, uint32_t* d_ids, uint32_t* d_totals,
              uint32_t* d_n_found) {
-  const uint32_t slots = m->dir_size, grid = std::min<uint32_t>(blocks_for(slots), POP_GRID_MAX);
-  x.p_ctl.need(1); x.p_keys.need(slots); x.p_out.need(n);
-  HIP_OK(hipMemsetAsync(x.p_ctl.p, 0, sizeof(PopCtl), s));
-  hipLaunchKernelGGL(k_pop_keys, dim3(grid), dim3(256), 0, s, m->d_dir, slots, m->arena.base, f, min_total, x.p_keys.p, x.p_ctl.p);
-  hipLaunchKernelGGL(k_pop_start, dim3(1), dim3(64), 0, s, x.p_ctl.p, n);
-  for (uint32_t pass = 0; pass < RkValue::DIGITS; pass++) {
-    hipLaunchKernelGGL(k_pop_hist, dim3(grid), dim3(256), 0, s, x.p_keys.p, slots, x.p_ctl.p, pass);
-    hipLaunchKernelGGL(k_pop_pick, dim3(1), dim3(64), 0, s, x.p_ctl.p, pass);
-  }
-  hipLaunchKernelGGL(k_pop_collect, dim3(grid), dim3(256), 0, s, x.p_keys.p, slots, x.p_ctl.p, n, x.p_out.p);
-  hipLaunchKernelGGL(k_pop_sort, dim3(1), dim3(POP_SORT_THREADS), 0, s, x.p_ctl.p, n, x.p_out.p, d_ids, d_totals, d_n_found);
+  const uint32_t* out = sel_run<RkValue>(x, s, m->dir_size, n, [&](uint32_t grid, uint32_t* keys, SelCtl<RkValue>* ctl) {
+    hipLaunchKernelGGL(k_pop_keys, dim3(grid), dim3(256), 0, s, m->d_dir, m->dir_size, m->arena.base, f, min_total, keys, ctl);
+  });
+  hipLaunchKernelGGL(k_pop_sort, dim3(1), dim3(POP_SORT_THREADS), 0, s, sel_ctl<RkValue>(x), n, out, d_ids, d_totals, d_n_found);
   HIP_OK(hipGetLastError());
 }
 

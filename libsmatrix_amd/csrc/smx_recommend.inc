@@ -75,10 +75,10 @@ struct RecScratch {
   DevBuf<uint32_t> h_grp;                            // ... and the grouped call's: the group of every id
   DevBuf<uint32_t> h_scp, h_scgr;                    // ... and the scoped call's: its own map, the sessions' scope lists
   DevBuf<uint64_t> h_scoff;
-  DevBuf<PopCtl> p_ctl;                              // ... and the popular call's (smx_popular.inc): the select's state, a key per
-  DevBuf<unsigned long long> p_keys, p_out;          // directory slot, the n keys collected (ids: h_ids, totals: h_counts, n: h_nsc)
-  DevBuf<SelCtl<RkCosine>> t_ctl;                    // ... and the trending call's (smx_trending.inc): the select's state, three words
-  DevBuf<uint32_t> t_keys, t_out;                    // per slot of the directory, per key collected (its answers: h_ids, h_scores, h_counts, h_ranks, h_nsc)
+  // ... and the dense select's (sel_run in smx_popular.inc; kernels/select.hpp): the words of the SelCtl<P> asked for, P::W words per
+  // directory slot and per key collected.  One set for the popular and the trending call: a call holds the matrix lock and queues
+  // behind `done` of the call before it, so no two selects are in flight on one matrix
+  DevBuf<uint32_t> sel_ctl, sel_keys, sel_out;
   hipEvent_t done = nullptr;                         // recorded behind the last call's work (its stream may be any)
   // EVERY buffer above, and the only list of them: the trim, the "any buffer big" test and the release are this visitor's
   template <typename Fn>
@@ -86,7 +86,7 @@ struct RecScratch {
     f(ctl); f(lds_list); f(big_list); f(gk); f(owner); f(zpos); f(cnt); f(li); f(big_off); f(tlg); f(gq); f(gs); f(lk); f(scan); f(part);
     f(h_items); f(h_ids); f(h_counts); f(h_off); f(h_scores); f(h_w); f(h_exoff); f(h_ex); f(h_deny); f(h_toff); f(h_tg); f(h_ranks);
     f(h_eoff); f(e_ra); f(e_cb); f(h_amt); f(i_cnt); f(i_soff); f(i_part); f(h_opoff); f(h_foff); f(h_fill); f(h_nsc); f(h_grp); f(h_scp); f(h_scgr); f(h_scoff);
-    f(p_ctl); f(p_keys); f(p_out); f(t_ctl); f(t_keys); f(t_out);
+    f(sel_ctl); f(sel_keys); f(sel_out);
   }
 };
 

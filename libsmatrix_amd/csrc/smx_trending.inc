@@ -1,11 +1,11 @@
 // smx_trending.inc -- the trending items (include/smatrix_batch.h smatrix_cf_trending / _dev), host side.  Included by
-// smx_runtime.hip inside the translation unit, after smx_popular.inc (the popular call's limits and its RecCall with stage_filter;
-// the scratch is RecScratch's t_ctl / t_keys / t_out); the device code is kernels/trending.hpp.
+// smx_runtime.hip inside the translation unit, after smx_popular.inc (sel_run, pop_args_ok and its RecCall with stage_filter; the
+// scratch is RecScratch's sel_*); the device code is kernels/trending.hpp.
 //
 // trend_call is both flavours: a RecCall on `now` (its lock, its mirror written back, the scratch behind the previous read-path
 // call's work, the synchronisation rule and the trim at finish) with base's lock taken in address order around it -- mg_merge's
-// rule -- and base's mirror written back.  Inside it trend_run enqueues, with no read-back anywhere:
-//   k_trend_keys, k_sel_start, RkCosine::DIGITS times (k_sel_hist, k_sel_pick), k_sel_collect, k_trend_sort
+// rule -- and base's mirror written back.  Inside it trend_run enqueues, with no read-back anywhere, k_trend_keys, the dense select
+// (sel_run) and k_trend_sort.
 // Scratch: 12 bytes per slot of now's directory (the keys, three planes of words), 12 n bytes (the keys collected), SelCtl.
 // The host flavour stages the bitmap and copies the answers back.
 
@@ -20,17 +20,11 @@ struct TrendOut {
 };
 
 void trend_run(Matrix* m, RecScratch& x, hipStream_t s, const RecFilt& f, const TrendArgs& t, uint32_t n, const TrendOut& o) {
-  const uint32_t slots = m->dir_size, grid = std::min<uint32_t>(blocks_for(slots), POP_GRID_MAX);
-  x.t_ctl.need(1); x.t_keys.need((size_t)slots * TrendKey::W); x.t_out.need((size_t)n * TrendKey::W);
-  HIP_OK(hipMemsetAsync(x.t_ctl.p, 0, sizeof(SelCtl<TrendKey>), s));
-  hipLaunchKernelGGL(k_trend_keys, dim3(grid), dim3(256), 0, s, m->d_dir, slots, m->arena.base, f, t, x.t_keys.p, x.t_ctl.p);
-  hipLaunchKernelGGL(k_sel_start<TrendKey>, dim3(1), dim3(64), 0, s, x.t_ctl.p, n);
-  for (uint32_t pass = 0; pass < TrendKey::DIGITS; pass++) {
-    hipLaunchKernelGGL(k_sel_hist<TrendKey>, dim3(grid), dim3(256), 0, s, x.t_keys.p, slots, x.t_ctl.p, pass);
-    hipLaunchKernelGGL(k_sel_pick<TrendKey>, dim3(1), dim3(64), 0, s, x.t_ctl.p, pass);
-  }
-  hipLaunchKernelGGL(k_sel_collect<TrendKey>, dim3(grid), dim3(256), 0, s, x.t_keys.p, slots, x.t_ctl.p, n, x.t_out.p);
-  hipLaunchKernelGGL(k_trend_sort, dim3(1), dim3(POP_SORT_THREADS), 0, s, x.t_ctl.p, n, x.t_out.p, m->d_dir, slots - 1, m->arena.base, t,
+  const uint32_t slots = m->dir_size;
+  const uint32_t* out = sel_run<TrendKey>(x, s, slots, n, [&](uint32_t grid, uint32_t* keys, SelCtl<TrendKey>* ctl) {
+    hipLaunchKernelGGL(k_trend_keys, dim3(grid), dim3(256), 0, s, m->d_dir, slots, m->arena.base, f, t, keys, ctl);
+  });
+  hipLaunchKernelGGL(k_trend_sort, dim3(1), dim3(POP_SORT_THREADS), 0, s, sel_ctl<TrendKey>(x), n, out, m->d_dir, slots - 1, m->arena.base, t,
                      o.ids, o.scores, o.totals, o.expected, o.n_found);
   HIP_OK(hipGetLastError());
 }

@@ -1,4 +1,4 @@
-"""The kernels that smatrix_cf_trending adds (kernels/trending.hpp k_trend_*, k_sel_*<RkCosine>) are in the library, spill no register
+"""The kernels that smatrix_cf_trending runs (kernels/trending.hpp k_trend_*, kernels/select.hpp k_sel_*<RkCosine>) are in the library, spill no register
 and use no scratch memory, and keep the register counts of the build they were written with (no GPU needed: the counts are read from
 the gfx950 code object in smatrix.so through tools/kernel_regs.py, as tests/test_cf_fill_kernel_regs.py does).
 
@@ -10,9 +10,9 @@ VGPRs of that build, and the bound: the count rounded up to the granule of 8 reg
     k_sel_pick<RkCosine>       12 -> 16    one wave
     k_sel_collect<RkCosine>    24          streaming; a ballot per wave, one atomic per workgroup that takes any key
     k_trend_sort               23 -> 24    one 1024-lane workgroup, 48 KiB of LDS, two look-ups per result entry
-Next to them the popular call's kernels print 17, 4, 16, 12, 22 and 11: the 96-bit key costs two to twelve registers and no class of
-waves per SIMD.  The call adds kernels of its own and changes none: tests/test_cf_fill_kernel_regs.py and the other *_kernel_regs
-files, unchanged, pin what the other kernels print."""
+Next to them the popular call's kernels (k_pop_keys, k_sel_*<RkValue>, k_pop_sort) print 17, 2, 16, 12, 22 and 11: the 96-bit key costs
+two to twelve registers and no class of waves per SIMD.  tests/test_cf_fill_kernel_regs.py pins those, and the other *_kernel_regs
+files what the other kernels print."""
 from tests.test_merge_sim_kernel_regs import counts
 
 NEW = {
@@ -35,6 +35,6 @@ def test_the_new_kernels_are_present_spill_nothing_and_keep_their_registers():
     assert NEW["smx::k_trend_sort"] <= 128                                # a 1024-lane workgroup cannot launch with more
 
 
-def test_the_select_is_instantiated_for_the_96_bit_key_alone():
+def test_the_select_is_instantiated_for_the_96_bit_and_the_64_bit_key_and_no_other():
     seen, _ = counts("smx::k_sel_")
-    assert sorted(seen) == sorted(k for k in NEW if "k_sel_" in k)
+    assert sorted(seen) == sorted("smx::k_sel_%s<smx::%s>" % (k, p) for k in ("start", "hist", "pick", "collect") for p in ("RkCosine", "RkValue"))

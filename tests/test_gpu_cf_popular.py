@@ -160,6 +160,27 @@ def test_a_total_set_through_the_scalar_call_counts_at_once():
     m.close()
 
 
+@pytest.mark.parametrize("n", [1, 100, 299])
+def test_equal_large_totals_take_the_select_down_into_the_id_bytes(n):
+    """About 300 rows of ONE total, 0xFF000001, and five of 0xFF000002: the select starts at digit 7 and the totals decide nothing
+    below digit 4, so every cut falls among the id bytes.  The two smallest ids of the five differ in their last byte alone: n = 1
+    finds two keys in its bin at digits 3, 2 and 1 and ends at digit 0, after all eight passes."""
+    rng = np.random.default_rng(97)
+    ids = np.unique(rng.integers(1 << 20, 0xFFFFFFFF, 300, dtype=np.uint64).astype(np.uint32))
+    five = np.array([0x00012301, 0x00012302, 0x4d000007, 0x9e3779b9, 0xf0000001], np.uint32)
+    assert not np.isin(five, ids).any() and ids.size + five.size > 300
+    x = np.concatenate([ids, five])
+    m = SparseMatrix()
+    m.apply_batch(SET, x, np.zeros(x.size, np.uint32), np.where(np.isin(x, five), 0xFF000002, 0xFF000001).astype(np.uint32), results=False)
+    want = F.popular(m.export("sorted"), n)
+    assert want[0].size == n and want[0][0] == 0x00012301
+    check(m.cf_popular(n), want, ("host", n))
+    d_ids, d_tot, nf = popular_dev(m, n)
+    assert nf == n
+    check((d_ids, d_tot), want, ("dev", n))
+    m.close()
+
+
 def test_an_empty_matrix_and_every_id_denied():
     m = SparseMatrix()
     ids, tot = m.cf_popular(64)
