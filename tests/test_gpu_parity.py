@@ -12,6 +12,7 @@ import pytest
 
 from libsmatrix_amd.stream import Stream
 from tests import replay
+from tests.write_batch_helpers import per_key_sorted, state_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +27,6 @@ def G():
 
 def sha(a):
     return hashlib.sha256(np.asarray(a).astype("<u4").tobytes()).hexdigest()
-
-
-def per_key_sorted(x, y, ret):
-    k = x.astype(np.uint64) << 32 | y.astype(np.uint64)
-    o = np.lexsort((ret, k))
-    return k[o], ret[o]
-
-
-def state_equal(g, o, rows, exact_layout):
-    for x in rows:
-        gi, oi = g.row_info(x), o.row_info(x)
-        assert gi == oi, ("row_info", x, gi, oi)
-        a, b = np.asarray(g.row_slots(x)), np.asarray(o.row_slots(x))
-        if exact_layout:
-            assert (a == b).all(), ("layout", x)
-        else:
-            ka = a[(a[:, 0] != 0) | (a[:, 1] != 0)]; kb = b[(b[:, 0] != 0) | (b[:, 1] != 0)]
-            ka = ka[np.lexsort((ka[:, 1], ka[:, 0]))]; kb = kb[np.lexsort((kb[:, 1], kb[:, 0]))]
-            assert ka.shape == kb.shape and (ka == kb).all(), ("content", x)
-            # and the table must be a valid `key % size` linear-probe layout (src/smatrix.c:363-380)
-            size = a.shape[0]
-            for p in np.nonzero(a[:, 0])[0]:
-                q = int(a[p, 0]) % size
-                while q != p:
-                    assert a[q, 0] != 0 or a[q, 1] != 0, ("probe chain broken", x, int(a[p, 0]))
-                    q = (q + 1) % size
 
 
 # ---------------------------------------------------------------------------
